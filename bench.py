@@ -7,11 +7,19 @@ L2 normalise, exactly the launch chain ArcFace.process runs.  N GPUs = N indepen
 pool (weak scaling, no data-path collective: images are independent).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (implicit-GEMM conv
-kernel: algorithmic FLOPs / HIP-event kernel time, vs the 2.5 PFLOP/s dense bf16 MFMA peak) and
-`cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+--steps steps of the headline workload and prints the line (`value`, `ms_per_step`, ...) — nothing else.
+--full adds every other leg: `roofline` (implicit-GEMM conv kernel: algorithmic FLOPs / HIP-event kernel
+time, vs the 2.5 PFLOP/s dense bf16 MFMA peak), `cpu_baseline` (the CPU oracle timed on the host's
+cores on a bounded sample), the exact-selection rate, the config-1 / 3 / 4 / 5 legs, the fine-tune and
+single-image timings and the parity checks against batch-1 rows and the CPU oracle.
+
+--dump-outputs DIR writes what the last timed step computed — the (batch, 512) float32 embeddings a caller
+of IRBackbone.embed_device receives — as DIR/embeddings.npy (rank k > 0: DIR/embeddings_rank<k>.npy).
+Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -264,7 +272,13 @@ def main():
     ap.add_argument("--select-dtype", default="f16x2", choices=["f16x2", "f32", "none"], help="the exact-selection leg: the same "
                     "workload in the mode whose active-learning selection sets equal the f32 arithmetic's (DESIGN.md §5), reported "
                     "as `exact_selection` beside the headline; also the committee's dtype in the config-3 leg")
+    ap.add_argument("--full", action="store_true", help="run every leg beside the headline (exact selection, config 1 / 3 / 4 / 5, "
+                    "roofline, fine-tune and single-image timings, CPU baseline, parity checks); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the embeddings of the last "
+                    "timed step as DIR/embeddings.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_launch_ranks(args.gpus))
 
@@ -370,12 +384,19 @@ def main():
         dt = float(t.item())
     bb.check_range()
     assert torch.isfinite(out).all()
-    # parity of what was just timed (cheap part, every rank): images embedded ALONE (batch 1: the 64-channel form of
-    # the linear-tile kernel) must equal their rows of the timed batch (128-channel form, launches on several streams) bit for bit
-    probe = sorted(set([0, 1, min(B - 1, args.chunk - 1), min(B - 1, args.chunk), B - 1]))
-    alone = torch.cat([bb.embed_device(x[i:i + 1]) for i in probe])
-    parity = {"batch1_rows_bit_equal_to_timed_batch": bool(torch.equal(alone, out[probe])), "rows_checked": probe}
-    assert parity["batch1_rows_bit_equal_to_timed_batch"], "embedding depends on the batch it was computed in"
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "embeddings.npy" if rank == 0 else "embeddings_rank%d.npy" % rank),
+                out.cpu().numpy().astype(np.float32))
+    extras = args.full and not args.no_extras
+    parity = None
+    if args.full:
+        # parity of what was just timed (cheap part, every rank): images embedded ALONE (batch 1: the 64-channel form of
+        # the linear-tile kernel) must equal their rows of the timed batch (128-channel form, launches on several streams) bit for bit
+        probe = sorted(set([0, 1, min(B - 1, args.chunk - 1), min(B - 1, args.chunk), B - 1]))
+        alone = torch.cat([bb.embed_device(x[i:i + 1]) for i in probe])
+        parity = {"batch1_rows_bit_equal_to_timed_batch": bool(torch.equal(alone, out[probe])), "rows_checked": probe}
+        assert parity["batch1_rows_bit_equal_to_timed_batch"], "embedding depends on the batch it was computed in"
 
     from oracle import ir_resnet     # FLOP count + cpu_baseline leg only
     gflop_per_emb = ir_resnet.flops_per_image(units) / 1e9
@@ -414,7 +435,7 @@ def main():
                                      "screen-then-settle": "identical on every workload measured (16-bit screening + split precision near the cuts, under "
                                                            "a MEASURED error bound with a sampled audit: config3 / config4 .audit; not a theorem)"},
         "headline_mode_note": "value is the %s SCREENING rate; the rate with selection sets identical to the float32 arithmetic is "
-                              "exact_selection (every image exact) and config3.screen_settle (exact only near a cut)" % args.dtype
+                              "exact_selection (every image exact) and config3.screen_settle (exact only near a cut), both measured by --full" % args.dtype
                               if args.dtype in ("bf16", "f16") else None,
     }
 
@@ -538,14 +559,14 @@ def main():
             ts.append(time.perf_counter() - t1)
         return 1e3 * float(np.median(ts))
 
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         line["single_image_ms"] = single_image_ms(bb)
         line["single_image_note"] = ("one image, host in / host out, %s; launches of a handful of images take the latency form of the 3x3 convolution "
                                      "(csrc/conv3x3_lat.hip), bit-identical to the batched kernels (parity.batch1_rows_bit_equal_to_timed_batch)" % args.dtype)
 
     sel_out = None
     smallres_weights = None
-    if args.select_dtype != "none" and args.select_dtype != args.dtype:
+    if args.full and args.select_dtype != "none" and args.select_dtype != args.dtype:
         # ---- the exact-selection leg (north_star: ">= 10 k embeddings/s ... with selection sets identical to the
         # reference"): the SAME images through the mode whose selection sets equal the f32 arithmetic's — split precision
         # (f16 pairs, three products on the f16 matrix cores, power-of-two scales calibrated per tensor) unless --select-dtype f32
@@ -582,15 +603,15 @@ def main():
                     "both columns equal at IR-50 and IR-100 depth)"}
         line["value_exact"] = {"embeddings_per_s": sel_rate, "dtype": args.select_dtype, "same_workload_as_value": True,
                                "note": "every image in the mode whose embeddings equal the f32 oracle's to float32 accuracy (exact_selection)"}
-        if rank == 0 and not args.no_extras and args.select_dtype == "f16x2":
+        if rank == 0 and extras and args.select_dtype == "f16x2":
             # the exact mode's own dominant kernel: algorithmic fraction, issued fraction (3 MFMA FLOPs per algorithmic FLOP), traffic
             line["exact_selection"]["roofline"] = roofline_of(bs, "f16x2")
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and extras:
             line["exact_selection"]["single_image_ms"] = single_image_ms(bs)
         del bs
     del params
 
-    if dist is not None and not args.no_extras:
+    if dist is not None and extras:
         # ---- fine-tune step in a one-process-per-GPU job, both forms (a-link_amd/distributed.py):
         # sharded = the 16-pair batch split over the ranks, ONE RCCL all-reduce of the flat gradient buffer (+ metrics),
         # identical Adadelta update on every rank; replicated = every rank runs the whole batch, no collective
@@ -622,7 +643,7 @@ def main():
             del hdp
         line["finetune_step_dp_policy"] = "replicated below %d rows (a-link_amd/distributed.py)" % D.DP_SHARD_MIN_ROWS
 
-    if not args.no_config3 and not args.no_extras:
+    if extras and not args.no_config3:
         # ---- BASELINE configs[2] shape, this rank's share: a committee of THREE IR-50 backbones + heads over a pool shard
         # against a 16-image gallery, entropy, top-1024, one candidate exchange — three ways:
         #   screening      everything in the 16-bit mode (f16 where the activations fit, else bf16): the fast number, whose
@@ -740,7 +761,7 @@ def main():
         hds = trained
         del exa, scr, hds, shard, cal
 
-    if not args.no_configs1 and not args.no_extras:
+    if extras and not args.no_configs1:
         # ---- BASELINE configs[1] AS WORDED: "ResNet-50 ArcFace 512-d feature extraction, 112x112 batch=256, 1 MI355X" — IR-50,
         # ONE 256-image batch per step (one alink_embed call, split into two in-call shards by the library), in the screening
         # dtype and in the exact mode
@@ -764,7 +785,7 @@ def main():
         line["configs1"] = c1
         del p50
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         # ---- the boundary as the reference's callers use it: HOST arrays in, host arrays out (ArcFace.process on a NumPy pool,
         # reference code/siamese.py:232-234) — PCIe-inclusive, never `value`: uint8 pixels, uploads overlapped with compute
         hp = px[:B].numpy()
@@ -776,7 +797,7 @@ def main():
         line["pool_from_host_note"] = "IRBackbone.embed on a (%d,112,112,3) uint8 host array -> (N,512) host array, %s; PCIe-inclusive, not `value`" % (B, args.dtype)
         assert np.isfinite(eh).all()
 
-    if not args.no_config4 and not args.no_extras:
+    if extras and not args.no_config4:
         # ---- BASELINE configs[3] shape: ONE A-LINK iteration (reference code/ALINK_arc.py:142-254) with an IR-100
         # teacher — 16 persons x (2 plain + 3 disguised) = 80 unique images, P = 3,840 pairs, four noises drawn per pair
         # occurrence = 30,720 noisy embeddings (the bulk of an iteration), selection, fine-tune —
@@ -884,7 +905,7 @@ def main():
                                                  "to the all-exact iteration's in this run" if same4 else "config4.screen_settle (NOT identical in this run)",
                                                  "all_exact_embeddings_per_s": n_emb / t_e}
 
-    if not args.no_config5 and not args.no_extras:
+    if extras and not args.no_config5:
         # ---- BASELINE configs[4] ("A2-LINK: adversarial-noise batch"): the reference's adversarial noise is the black-box few-pixel
         # attack (code/noise.py:171-188 -> code/attack.py:91-103: 40 pixels, population 200, 50 generations = 20,400 backbone forwards per
         # pair), `adversarial` is in its default --noise list (code/ALINK_arc.py:41).  attack_all advances the pairs' searches in
@@ -950,7 +971,7 @@ def main():
                 "per_iteration_note": "a config-4-sized iteration has 3,840 pairs: x s_per_pair / n_gpus"})
         del conv5, stu5, wrapped5
 
-    if rank == 0 and not args.no_extras and args.dtype == "f32":
+    if rank == 0 and extras and args.dtype == "f32":
         # ---- float32 mode: every convolution and the FC on gemm32_kernel (v_mfma_f32_32x32x2_f32); no per-launch
         # profile entry for this mode, so the roofline is the whole forward of one launch batch between two HIP events
         # on the stream the kernels are launched on (torch's current stream), against the f32 matrix-core peak
@@ -969,7 +990,7 @@ def main():
                             "achieved": ach, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": ach / F32_MFMA_PEAK_TFLOPS,
                             "traffic": None, "flops_per_launch": args.chunk * gflop_per_emb * 1e9, "avg_launch_ms": fms,
                             "timing": "HIP events on the launch stream around one forward, median of 3"}
-    if rank == 0 and not args.no_extras and args.dtype != "f32":
+    if rank == 0 and extras and args.dtype != "f32":
         line["roofline"] = roofline_of(bb, args.dtype)
         # ---- fine-tune step (second half of BASELINE.json's metric): head-512, batch 16
         from a_link_amd.head import DenseHead
@@ -1070,7 +1091,7 @@ def main():
         smallres_weights = srn.get_weights()
         del srn
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle (kind "port": our CPU restatement; the reference's MXNet /
         # Keras path cannot be installed) on a bounded sample of the same workload, four legs
         from oracle import siamese_head as OH
@@ -1199,20 +1220,23 @@ def main():
             line["exact_selection"]["oracle_rows"] = int(nrow)
             assert line["exact_selection"]["max_abs_diff_vs_cpu_oracle"] < 2e-5, line["exact_selection"]
 
-    # which device every rank's handles live on (the C ABI's device rule: a handle belongs to the device current at its create
-    # call; rank k of a one-process-per-GPU job must see its models on GPU LOCAL_RANK), gathered from all ranks
-    from a_link_amd import _abi as _AB
-    mine = torch.tensor([rank, local_rank, torch.cuda.current_device(), int(bb.device),
-                         int(_AB.load().alink_backbone_device(bb.h))],
-                        dtype=torch.int32, device="cuda")
-    seen = [mine.clone() for _ in range(world)]
-    if dist is not None:
-        dist.all_gather(seen, mine)
-    seen = [t.cpu().tolist() for t in seen]
-    assert all(r[1] == r[2] == r[3] == r[4] for r in seen), "a rank's handle is not on its own device: %s" % seen
+    if args.full:
+        # which device every rank's handles live on (the C ABI's device rule: a handle belongs to the device current at its create
+        # call; rank k of a one-process-per-GPU job must see its models on GPU LOCAL_RANK), gathered from all ranks
+        from a_link_amd import _abi as _AB
+        mine = torch.tensor([rank, local_rank, torch.cuda.current_device(), int(bb.device),
+                             int(_AB.load().alink_backbone_device(bb.h))],
+                            dtype=torch.int32, device="cuda")
+        seen = [mine.clone() for _ in range(world)]
+        if dist is not None:
+            dist.all_gather(seen, mine)
+        seen = [t.cpu().tolist() for t in seen]
+        assert all(r[1] == r[2] == r[3] == r[4] for r in seen), "a rank's handle is not on its own device: %s" % seen
+        if rank == 0:
+            line["devices_seen"] = [{"rank": r[0], "local_rank": r[1], "current_device": r[2], "backbone_device": r[3], "handle_device": r[4]}
+                                    for r in seen]
+            line["parity"] = parity
     if rank == 0:
-        line["devices_seen"] = [{"rank": r[0], "local_rank": r[1], "current_device": r[2], "backbone_device": r[3], "handle_device": r[4]} for r in seen]
-        line["parity"] = parity
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

@@ -176,6 +176,11 @@ hipError_t launch_conv3x3_s2c64(int variant, int dtype, const ConvParams& p, hip
 bool       front_c64_applies(int dtype, int H, int W, int C0, int Cout);
 hipError_t front_c64_set_attributes();
 hipError_t launch_front_c64(int dtype, const ConvParams& conv1, const StemParams& stem, void* xs, bool slopes_le_1, hipStream_t st);
+// unit_c64.hip: a plain 56 x 56 x 64 residual unit (conv1 + PReLU, conv2 + residual) in one rolling-row launch, the
+// intermediate kept in LDS; c1 / c2 as the two conv3x3_linear launches it replaces would be made (c1.out is not written)
+bool       unit_c64_applies(int dtype, const ConvParams& c1, const ConvParams& c2);
+hipError_t unit_c64_set_attributes();
+hipError_t launch_unit_c64(int dtype, const ConvParams& c1, const ConvParams& c2, hipStream_t st);
 int        direct_variant_cpl(int v);
 hipError_t direct_set_attributes();
 hipError_t launch_conv3x3_direct(int variant, int dtype, const ConvParams& p, hipStream_t st);

@@ -784,6 +784,12 @@ int g_stagger = 0;
 int g_shard_stagger = 0;
 extern "C" void alink_debug_set_shard_stagger(int on) { g_shard_stagger = on; }
 
+// Plain stage-1 units (56 x 56 x 64, stride 1) as one launch (unit_c64.hip) in the 16-bit forward: 0 = off, 1 = from
+// FUSE_UNIT_MIN_N images per launch, 2 = at every batch size.  The persistent launch has one workgroup per pass-pair range;
+// below ~64 images a range is a handful of passes, and the two passes of lag between conv1 and conv2 dominate it.
+int g_fuse_unit = 1;
+constexpr int FUSE_UNIT_MIN_N = 64;
+extern "C" void alink_debug_set_fuse_unit(int mode) { g_fuse_unit = mode; }
 extern "C" void alink_debug_set_stagger(int n) { g_stagger = n < 0 ? 0 : n; }
 void* g_stamps = nullptr;
 // alink_embed_profile launches every kernel of the chain this many times back to back between its two
@@ -793,6 +799,23 @@ int g_prof_reps = 4;
 extern "C" void alink_debug_set_profile_reps(int n) { g_prof_reps = n < 1 ? 1 : n; }
 extern "C" void alink_debug_set_ablate(int a) { g_ablate = a; }
 extern "C" void alink_debug_set_stamps(void* p) { g_stamps = p; }
+
+// The conv2 that L (a plain unit's conv1) can share one unit_c64 launch with at batch N, or nullptr.  The linear-tile
+// variant 13 on both layers is what the fused launch reproduces (and it is only chosen where the LDS out-of-range probe
+// passed, which the fused kernel's border handling rests on too).
+static const ConvLayer* fusable_unit(const alink_backbone* bb, const ConvLayer& L, int N, int S, bool cache) {
+    if (!g_fuse_unit || (g_fuse_unit == 1 && N < FUSE_UNIT_MIN_N) || cache || S != 1 || g_ablate || g_stamps) return nullptr;
+    const int dt = bb->cfg.dtype;
+    if (dt != ALINK_DT_BF16 && dt != ALINK_DT_F16) return nullptr;
+    const size_t i = (size_t)(&L - bb->convs.data());
+    if (L.role != 1 || i + 1 >= bb->convs.size()) return nullptr;
+    const ConvLayer& L2 = bb->convs[i + 1];
+    if (L2.role != 3 || L2.unit != L.unit || L2.Cin2 || L2.in_buf != L.out_buf || L2.resid_buf != L.in_buf) return nullptr;
+    if (L.variant != 13 || L2.variant != 13 || L.stride != 1 || L2.stride != 1) return nullptr;
+    if (L.Cin != 64 || L.Cout != 64 || L2.Cin != 64 || L2.Cout != 64 || L.Hin != 56 || L.Win != 56) return nullptr;
+    if (plan_split(bb, L2, N) != 1) return nullptr;
+    return &L2;
+}
 
 // calib (ALINK_DT_F16X2 only): 0 = a normal forward; 1 = choose every tensor's scale exponent from this batch; 2 = the
 // same, never above the exponents already held (re-calibration after a batch left the range).  Synchronous when != 0.
@@ -819,6 +842,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
     const int cap = prof ? *n_launches : 0;
     int nl = 0;
     std::vector<hipEvent_t> ev;
+    std::vector<int> split_pairs;     // profile entries i, i + 1 that share one launch (a fused unit's conv1 and conv2)
     auto mark = [&]() -> int {
         if (!prof) return ALINK_OK;
         hipEvent_t e;
@@ -897,7 +921,9 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
 
     int last_out = 0, n_done = 0;
     bool front_marked = false;
+    bool skip_conv2 = false;                 // the layer before was a fused unit's conv1: this conv2 ran in its launch
     for (ConvLayer& L : bb->convs) {
+        if (skip_conv2) { skip_conv2 = false; continue; }
         if (g_stop_after && n_done++ >= g_stop_after) return ALINK_OK;
         if (front_done && !front_marked && L.stage >= 1) {       // everything before this launch is the HBM-bound front
             ALINK_HIP(hipEventRecord(front_done, stream));
@@ -963,6 +989,26 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             if ((rc = mark())) return rc;
             last_out = L.out_buf;
             continue;
+        } else if (const ConvLayer* L2 = fusable_unit(bb, L, N, S, cache != nullptr)) {
+            // a plain stage-1 unit: conv1 and conv2 in one launch (unit_c64.hip), t kept in LDS — the same sums as the two
+            // linear-tile launches, bit for bit
+            ConvParams p2 = p;
+            p2.in = buf(L2->in_buf); p2.wgt = L2->d_w; p2.bias = L2->d_bias; p2.alpha = L2->d_alpha;
+            p2.resid = buf(L2->resid_buf); p2.out = buf(L2->out_buf);
+            p2.Cout = L2->Cout; p2.border_cls = L2->border_cls ? 1 : 0;
+            ALINK_REQUIRE(unit_c64_applies(cfg.dtype, p, p2), ALINK_EINVAL, "fused unit %s: launch forms do not apply", L.name.c_str());
+            for (int r = 0; r < reps; ++r) ALINK_HIP(launch_unit_c64(cfg.dtype, p, p2, stream));
+            // the profile keeps one entry per convolution layer of the chain (bench.py's roofline maps entries to layer
+            // shapes): conv1 and conv2, each with its own FLOPs and half of the launch's time (the second event pair
+            // encloses no work; the two are evened out below)
+            note(conv_flops(p), 1);
+            if ((rc = mark())) return rc;
+            if (prof && nl < cap) split_pairs.push_back(nl - 1);
+            note(conv_flops(p2), 1);
+            if ((rc = mark())) return rc;
+            last_out = L2->out_buf;
+            skip_conv2 = true;
+            continue;
         } else
         for (int r = 0; r < reps; ++r) {
             ConvParams q = p;
@@ -1009,6 +1055,8 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             ALINK_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
             ms[i] = t / (float)reps;
         }
+        for (int i : split_pairs)
+            if (i + 1 < cap && i + 2 < (int)ev.size()) ms[i] = ms[i + 1] = 0.5f * (ms[i] + ms[i + 1]);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         *n_launches = nl;
     }

@@ -34,6 +34,9 @@ void alink_debug_set_c64(int on);
 void alink_debug_set_s2direct(int on);
 /* 0: stem and stage1_unit1 conv1 as two launches instead of the fused front kernel (front_c64.hip) */
 void alink_debug_set_fuse_stem(int on);
+/* plain 56 x 56 x 64 residual units (stage 1) in one launch, conv1's output kept in LDS (unit_c64.hip; 16-bit forward only):
+ * 0 = never (two conv3x3_linear launches), 1 = from the batch size the dispatch picks (default), 2 = at every batch size */
+void alink_debug_set_fuse_unit(int mode);
 /* 0: projection shortcuts as launches of their own instead of extra K-steps of conv2.  READ AT alink_backbone_create. */
 void alink_debug_set_fuse_shortcut(int on);
 /* 0: the implicit GEMM stages its tiles through registers (global_load -> ds_write) instead of LDS-DMA */

@@ -24,6 +24,7 @@ ap.add_argument("--no-fuse-stem", action="store_true", help="A/B: stem and stage
 ap.add_argument("--lib", default="", help="experiments: load this build of libalink_hip.so instead of the package's")
 ap.add_argument("--no-s2direct", action="store_true", help="A/B: stage1_unit1's stride-2 conv2 + shortcut on the implicit-GEMM kernel")
 ap.add_argument("--no-fuse-sc", action="store_true", help="A/B: projection shortcuts as launches of their own")
+ap.add_argument("--no-fuse-unit", action="store_true", help="A/B: plain stage-1 units as two linear-tile launches instead of one (unit_c64.hip)")
 ap.add_argument("--linear", type=int, default=-1, help="linear-tile widths: bit0 56, bit1 28, bit2 14, bit3 7 (default: library default)")
 a = ap.parse_args()
 units = W.ARCH_UNITS[a.model]
@@ -40,6 +41,8 @@ if a.linear >= 0:
     _lib.alink_debug_set_linear(a.linear)
 if a.no_fuse_sc:
     _lib.alink_debug_set_fuse_shortcut(0)
+if a.no_fuse_unit:
+    _lib.alink_debug_set_fuse_unit(0)
 if a.no_c64:
     _lib.alink_debug_set_c64(0)
 if a.no_fuse_stem:
@@ -57,6 +60,7 @@ fl = [f for _, _, f in profs[0]]
 # group identical (kind, flops) launches
 fused_sc = sum(1 for k in kinds if k == 1) == 2 * sum(units)     # projection shortcuts inside the conv2 launch
 fused_front = kinds[0] == 1                                       # stem inside the first conv launch (front_c64.hip)
+# (a fused stage-1 unit, unit_c64.hip, is reported as its conv1 and conv2, each with half of the launch's time)
 names = [] if fused_front else ["stem"]
 for s in range(4):
     for u in range(units[s]):

@@ -19,8 +19,15 @@ What changes is only where arithmetic runs and how often:
     but each noise is one kernel launch and each noisy batch one batched embed;
   * selection (code/ALINK_arc.py:167-198) is selection.select_queries: same rule, ties towards the
     lower index, queryIndices ascending (Python-2 `Set` order is arbitrary in the reference).
-`augment=True` (tf.contrib rotations + imgaug, code/helpers.py:114-141) is outside the hot path and
-raises NotImplementedError.
+`augment=True` is the reference's branch (code/ALINK_arc.py:233-238, ALINK.py:236-241): the queried pairs' pixels go
+through helpers.augment_data (code/helpers.py:114-141: the original plus rotated, sheared and shifted copies, drawn from
+np.random at the reference's place in the stream, after the mixture draws of the generator), the copies are converted
+in the exact mode (never the screening form: they feed the fine-tune) and take the place of the clean rows in the
+fine-tune set.  The warps of a side are one launch gathered straight out of the iteration's unique images; the original
+slots reuse the clean rows instead of embedding those images again.
+One deliberate repair: ALINK_MTP.py:245 passes the undefined `batch_x_left` (twice), so the reference's MTP branch cannot
+run.  Here it does what it evidently meant: it augments the queried pairs' low-res student inputs, left and right — the
+rows the branch without augmentation appends.
 """
 import numpy as np
 
@@ -139,9 +146,33 @@ def sync_host_randomness(ensembleNoise, shards):
             z.set_stream_state(st)
 
 
+def _augment_queries(q, labels, pixels, convert, clean_for_student):
+    """helpers.augment_data([left[q], right[q]], labels, 1) converted for the student (code/ALINK_arc.py:234-235), with the
+    pixels gathered straight out of `pixels` = ([left table, right table], [left rows, right rows]) by the warp launch of
+    each side.  The original slots take the clean rows clean_for_student[s][q] instead of converting those images again:
+    conversions are per-image deterministic.  Returns [left, right], labels."""
+    from . import augment
+    tables, index = pixels
+    q = np.asarray(q, np.int64)
+    H, W = int(tables[0].shape[1]), int(tables[0].shape[2])
+    plan = augment.draw(len(q), H, W, 1)
+    new = ~plan.original
+    sides = []
+    for s in (0, 1):
+        rows = _np(index[s]).astype(np.int64)[q]
+        feats = _np(convert(augment.warp(tables[s], rows[plan.src[new]], plan.maps[s][new], 1, plan.copy[s][new])))
+        clean = _np(clean_for_student[s])[q]
+        out = np.empty((len(plan.src),) + clean.shape[1:], clean.dtype)
+        out[plan.original] = clean[plan.src[plan.original]]
+        out[new] = feats
+        sides.append(out)
+    return sides, np.asarray(labels)[plan.src]
+
+
 def alink_iteration(state, flags, batch_x, batch_y, batch_x_features, bag, ensembleNoise, student, dataGen,
                     noisy_for_student, clean_for_student, image_res, col=0, verbose=1, labels_one_hot=False,
-                    noisy_for_student_screen=None, group=None, batch_x_rows=None, calibration_of=None):
+                    noisy_for_student_screen=None, group=None, batch_x_rows=None, calibration_of=None,
+                    augment_pixels=None):
     """One pass of the loop body (code/ALINK_arc.py:150-254) over an already-built mini-batch.
 
     batch_x            [left, right] pair images (P, H, W, 3)
@@ -176,6 +207,11 @@ def alink_iteration(state, flags, batch_x, batch_y, batch_x_features, bag, ensem
     calibration_of     optional f() -> a picklable calibration state of the feature model (ArcFace: the split-precision
                        scales): checked equal on all ranks before and after the iteration — a rank that re-calibrated on
                        its own rows would embed to different last bits than its peers.
+    augment_pixels     flags.augment (code/ALINK_arc.py:233-238): the pixels the queried pairs are augmented from, as
+                       ([left table, right table], [left rows, right rows]) — pair row p's side s is table_s[rows_s[p]];
+                       None: batch_x itself (which then has to hold all P rows).  With `group`, every rank augments and
+                       converts the SAME rows (replicated, like the clean pass; host randomness is in step, so the maps
+                       are too): sharding that conversion is not done.
     Returns the number of examples added to the pending fine-tune set, or -1 when the reference
     `continue`s (no query survived: code/ALINK_arc.py:203-205 — the stop check is skipped too).
     """
@@ -370,11 +406,26 @@ def alink_iteration(state, flags, batch_x, batch_y, batch_x_features, bag, ensem
             X_old_right = np.concatenate((X_old_right, X_old_temp[1]))
             Y_old = np.concatenate((Y_old, Y_old_temp))
         if flags.augment:
-            raise NotImplementedError("--augment (tf.contrib rotations + imgaug, code/helpers.py:114-141) is outside "
-                                      "the hot path and not built")
-        left = np.concatenate((state.left, _np(clean_for_student[0])[q], X_old_left))
-        right = np.concatenate((state.right, _np(clean_for_student[1])[q], X_old_right))
-        y = np.concatenate((state.y, labels, Y_old))
+            # code/ALINK_arc.py:233-238: the queried pairs' pixels augmented (helpers.augment_data, factor 1) and converted
+            # like the noisy copies; they take the place of the clean rows
+            if augment_pixels is None:
+                if batch_x_rows is not None:
+                    raise ValueError("alink_iteration: flags.augment needs augment_pixels when batch_x holds only this rank's rows")
+                augment_pixels = ([batch_x[0], batch_x[1]], [np.arange(P), np.arange(P)])
+            cal_a = calibration_of() if calibration_of is not None else None
+            (aug_left, aug_right), aug_y = _augment_queries(q, labels, augment_pixels, lambda p: convert(noisy_for_student, p),
+                                                            clean_for_student)
+            if calibration_of is not None and calibration_of() != cal_a:
+                # the copies are the same images on every rank, so a re-calibration they cause happens on every rank alike
+                state.recalibrations += 1
+                log("note: the feature model re-calibrated its split-precision scales while embedding the augmented copies")
+            left = np.concatenate((state.left, aug_left, X_old_left))
+            right = np.concatenate((state.right, aug_right, X_old_right))
+            y = np.concatenate((state.y, aug_y, Y_old))
+        else:
+            left = np.concatenate((state.left, _np(clean_for_student[0])[q], X_old_left))
+            right = np.concatenate((state.right, _np(clean_for_student[1])[q], X_old_right))
+            y = np.concatenate((state.y, labels, Y_old))
         net = getattr(student, "siamese_net", None)
         if shards is not None and net is not None and hasattr(net, "dp_group"):
             net.dp_group = group              # fit() -> distributed.dp_train_on_batch, rank 0's shuffles
@@ -421,7 +472,8 @@ def run_alink_dfw(flags, conversionModel, bag, ensembleNoise, disguisedFacesMode
     group (one process per GPU; see alink_iteration): every rank is handed the SAME data and models (same weights, same
     calibration) and calls this together; each materialises only its own rows of an iteration's pair batch, the state
     returned — and the student's weights — are the same on every rank and equal the single-process loop's.  Rank 0
-    alone writes `flags.out_model`."""
+    alone writes `flags.out_model`.  flags.augment: the iteration is handed the unique images and the pair indices, so that
+    every rank can augment and embed any queried row (replicated on every rank; alink_iteration)."""
     log = print if verbose else (lambda *a, **k: None)
     assert 0 <= flags.disparity_ratio <= 1 and 0 <= flags.eps < 0.5
     state = state or LoopState()
@@ -452,7 +504,8 @@ def run_alink_dfw(flags, conversionModel, bag, ensembleNoise, disguisedFacesMode
                                         disguisedFacesModel, dataGen, noisy_for_student=conversionModel.process,
                                         clean_for_student=batch_x_features, image_res=image_res, col=col, verbose=verbose,
                                         noisy_for_student_screen=getattr(conversionModel, "process_screen", None),
-                                        group=group, batch_x_rows=rows, calibration_of=probe)
+                                        group=group, batch_x_rows=rows, calibration_of=probe,
+                                        augment_pixels=([unique, unique], [li, ri]))
                 break
             except Recalibrated:
                 #  noisy images left the calibrated range on some rank, which lowered ITS scales: every rank takes
@@ -501,7 +554,9 @@ def run_alink_mtp(flags, conversionModel, bag, ensembleNoise, lowResModel, X_dig
     high-res features, the student (SmallRes) sees noisy LOW-res pixels and is fine-tuned on them.
     group: as in run_alink_dfw; the student's fine-tune goes through distributed.dp_train_on_batch like the head's (SmallResNet
     has the same four-method side of it): replicated at the reference's batch of 16 (every rank holds the same SmallRes and draws
-    the same mask seed), sharded with one exchange of the 20 MB gradient buffer from SmallResNet.DP_SHARD_MIN_ROWS rows."""
+    the same mask seed), sharded with one exchange of the 20 MB gradient buffer from SmallResNet.DP_SHARD_MIN_ROWS rows.
+    flags.augment: the queried pairs' LOW-res inputs are augmented (a repair of code/ALINK_MTP.py:245: see the module
+    docstring), warped out of the iteration's unique low-res images."""
     from . import noise as _noise
     log = print if verbose else (lambda *a, **k: None)
     state = state or LoopState()
@@ -532,7 +587,8 @@ def run_alink_mtp(flags, conversionModel, bag, ensembleNoise, lowResModel, X_dig
             batch_x = [unique[li], unique[ri]]
         added = alink_iteration(state, flags, batch_x, batch_y, [feats[li], feats[ri]], bag, ensembleNoise, lowResModel,
                                 dataGen, noisy_for_student=lambda p: np.asarray(p), clean_for_student=[low[li], low[ri]],
-                                image_res=low_res, col=0, verbose=verbose, labels_one_hot=True, group=group, batch_x_rows=rows)
+                                image_res=low_res, col=0, verbose=verbose, labels_one_hot=True, group=group, batch_x_rows=rows,
+                                augment_pixels=([low, low], [li, ri]))
         if added < 0:
             log("== Nothing in this set. Skipping batch ==")
             continue

@@ -507,6 +507,17 @@ int alink_perturb_images(const float* dev_img, const double* dev_xs, int n, int 
  * candidates [g * group, (g + 1) * group) perturb image dev_img_of[g] (int32, device; NULL: image 0 for all). */
 int alink_perturb_images_multi(const float* dev_imgs, const int* dev_img_of, int group, const double* dev_xs, int n,
                                int k, int Hc, int W, int split, float* dev_out, void* stream);
+/* helpers.augment_data (code/helpers.py:114-141): the affine resampling behind keras_preprocessing's random_rotation /
+ * random_shear / random_shift, i.e. scipy.ndimage.affine_transform(channel, A, offset, order, mode='nearest') on every
+ * channel, for n_out output images in one launch.  Output i reads image dev_src[i] (int32, device; NULL: image i) of the
+ * table dev_in (n_in, H, W, C) float32; its pixel (r, c) samples the source at
+ *   y = (r m00 + c m01) + m02,  x = (r m10 + c m11) + m12      (dev_mat[i] = {m00, m01, m02, m10, m11, m12}, float64)
+ * with each coordinate clamped to [0, n - 1]; order 1 interpolates bilinearly, order 0 takes the nearest tap.  All of it in
+ * float64 with scipy's operation order: the float32 results equal scipy's bit for bit.  dev_copy[i] != 0 (uint8, device;
+ * NULL: none) makes output i a byte copy of its source (Keras returns the input untouched when a drawn parameter is 0).  A
+ * source index outside [0, n_in) yields a row of NaN.  dev_out (n_out, H, W, C) must not overlap dev_in. */
+int alink_affine_warp(const float* dev_in, int n_in, const int32_t* dev_src, const double* dev_mat, const uint8_t* dev_copy,
+                      int n_out, int H, int W, int C, int order, float* dev_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * EXTENSIONS — named by BASELINE.json's north_star, ABSENT from the reference: the reference

@@ -24,6 +24,8 @@ def build_parser():
                    help="checkpoint prefix (code/ALINK_arc.py:64) or synthetic:<arch>")
     p.add_argument("--feature_model", default="arcface", choices=["arcface", "resnet50"])
     p.add_argument("--resnet50_weights", default=None, help="keras-vggface weight file for --feature_model resnet50")
+    p.add_argument("--grad_dtype", default="bf16", choices=["bf16", "f16"],
+                   help="storage type of the input-gradient pass that --noise fgsm / pgd run through (an extension)")
     p.add_argument("--pretrain_steps", type=int, default=320000, help="n_steps of customTrainModel (code/siamese.py:81)")
     p.add_argument("--quiet", action="store_true")
     return p
@@ -32,12 +34,15 @@ def build_parser():
 def main(argv=None):
     FLAGS = build_parser().parse_args(argv)
     verbose = 0 if FLAGS.quiet else 1
+    # the gradient noises need a feature model with an input-gradient pass: a second handle in --grad_dtype, built only then
+    wants_grad = any(n.lower() in ("fgsm", "pgd") for n in FLAGS.noise.split(','))
+    grad_dtype = FLAGS.grad_dtype if wants_grad else None
     if FLAGS.feature_model == "arcface":
         IMAGERES, FEATURERES, col = (112, 112), (512,), 0
-        conversionModel = siamese.ArcFace(IMAGERES, FLAGS.arcface_model)
+        conversionModel = siamese.ArcFace(IMAGERES, FLAGS.arcface_model, grad_dtype=grad_dtype)
     else:
         IMAGERES, FEATURERES, col = (224, 224), (2048,), 1
-        conversionModel = siamese.RESNET50(IMAGERES, weights=FLAGS.resnet50_weights)
+        conversionModel = siamese.RESNET50(IMAGERES, weights=FLAGS.resnet50_weights, grad_dtype=grad_dtype)
     (X_plain, X_dig, X_imp) = readDFW.getAllTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES, conversionModel)
     (X_plain_raw, X_dig_raw) = readDFW.getRawTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES)
     assert 0 <= FLAGS.split_ratio <= 1 and 0 <= FLAGS.disparity_ratio <= 1 and 0 <= FLAGS.eps < 0.5

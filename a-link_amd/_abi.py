@@ -70,6 +70,11 @@ PROTOTYPES = {
     "alink_resnet50_num_scales": (_i, [_vp]),
     "alink_resnet50_get_scales": (_i, [_vp, _vp, _i]),
     "alink_resnet50_set_scales": (_i, [_vp, _vp, _i]),
+    "alink_resnet50_enable_grad": (_i, [_vp]),
+    "alink_resnet50_grad_workspace_bytes": (_sz, [_vp, _i]),
+    "alink_resnet50_embed_cached": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "alink_resnet50_input_grad": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "alink_resnet50_input_grad_profile": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, C.POINTER(_i)]),
     "alink_resnet50_profile": (_i, [_vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_i)]),
     "alink_resnet50_op_name": (C.c_char_p, [_vp, _i]),
     "alink_vgg16_create": (_vp, [_i, _i, _i]),

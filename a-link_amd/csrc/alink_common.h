@@ -205,6 +205,18 @@ hipError_t launch_zero_insert(int dtype, const void* in, void* out, int N, int H
 hipError_t launch_stem_bwd(int dtype, const void* dy0, const void* y0, const float* w, const float* alpha, float* dpix,
                            int N, int H, int W, float mul, int nchw, hipStream_t st);
 
+// resnet50_bwd.hip (input-gradient pass of the VGGFace2 ResNet-50); scale = {2^e, 2^-e} in device memory
+hipError_t launch_r50_grad_scale(const float* dfeat, int count, int HW, float* scale, hipStream_t st);
+hipError_t launch_r50_avgpool_bwd(int dtype, const float* dfeat, const void* y, void* dz, const float* scale, int N, int HW, int C,
+                                  hipStream_t st);
+hipError_t launch_r50_relu_mask(int dtype, void* g, const void* y, long long count, hipStream_t st);
+hipError_t launch_r50_scatter_mask(int dtype, const void* in, const void* y, void* out, int N, int H, int W, int Ho, int Wo, int C,
+                                   hipStream_t st);
+hipError_t launch_r50_maxpool_bwd(int dtype, const void* y0, const void* pooled, const void* g, void* d0, int N, int H, int W, int C,
+                                  int Hp, int Wp, hipStream_t st);
+hipError_t launch_r50_stem_bwd(int dtype, const void* d0, const void* wfrag, float* dpix, const float* scale, int N, int H, int W,
+                               int Ho, int Wo, int pad_t, int pad_l, int flip, hipStream_t st);
+
 // host-side conversions
 uint16_t f32_to_bf16_rne(float f);
 uint16_t f32_to_f16_rne(float f);

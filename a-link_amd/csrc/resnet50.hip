@@ -17,6 +17,9 @@
 // unit's final ReLU as `post_relu`.  New here: the 7x7/2 stem (MFMA, K = 7 rows x 24 = 168 padded to
 // 192, input band mean-subtracted into LDS with a true-zero frame for TensorFlow's asymmetric 'same'
 // padding 2/3), the 3x3/2 max-pool and the 7x7 average pool.
+//
+// Input gradients (FGSM / PGD extension; 16-bit modes): alink_resnet50_enable_grad .. alink_resnet50_input_grad at the end of
+// this file walk the units backwards on the same convolution kernels; the kernels without a forward twin are in resnet50_bwd.hip.
 #include "alink_common.h"
 
 #include <algorithm>
@@ -358,6 +361,18 @@ struct Op {
     int in_buf = -1, out_buf = -1, resid_buf = -1;
     int e_w = 0, e_out = 0;   // split precision: stored value = true value x 2^e (weights: fixed at finalize; output: calibrated)
     std::string name;
+    // input-gradient pass (alink_resnet50_enable_grad)
+    void* d_wb = nullptr;     // kind 2: T [Cin][k*k*Cout], the transposed (3x3: flipped) folded weights, rows permuted for `bvariant`
+    int bvariant = 0;         // direct variant of the backward convolution (0 = conv_igemm)
+    int unit = -1, role = 0;  // kind 2: index of the bottleneck unit; 1 1x1_reduce, 2 3x3, 3 1x1_increase, 4 1x1_proj
+    int slot = -1;            // cached forward: which slot of the activation cache keeps this op's output (-1: scratch)
+};
+
+// gradient-mode workspace: [activation cache: one slot per kept op output][scratch: the projections' outputs][4 gradient
+// buffers of the largest map][the call's gradient scale]
+struct R50GradLayout {
+    std::vector<size_t> slot;
+    size_t scratch, g[4], scale, total;
 };
 
 }  // namespace
@@ -384,6 +399,10 @@ struct alink_resnet50 {
     int stem_e_w = 0;
     unsigned* d_absmax = nullptr;
     int *h_flag = nullptr, *d_flag = nullptr;      // pinned word the average-pool kernel raises on a non-finite feature
+    // input-gradient support
+    bool grad = false;
+    void* d_stem_wfrag = nullptr;        // folded stem weights by tap, as the matrix-core fragments of the stem backward
+    std::vector<size_t> slot_elems;      // per image, per cache slot
     std::vector<void*> allocs;
     ~alink_resnet50() {
         for (void* p : allocs) (void)hipFree(p);
@@ -427,7 +446,7 @@ void bn_fold(const alink_resnet50* r, const std::string& n, std::vector<double>&
 
 // Keras kernel (kh, kw, in, out) + following BN -> permuted T rows + f32 bias; appends a conv op
 int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int cin, int cout, int Hin, int Win,
-             int in_buf, int out_buf, int resid_buf, bool relu, bool post_relu) {
+             int in_buf, int out_buf, int resid_buf, bool relu, bool post_relu, int unit, int role) {
     const auto& w = r->raw.at(name + "/kernel");
     std::vector<double> a, b;
     bn_fold(r, name, a, b);
@@ -476,6 +495,31 @@ int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int 
     p.H = Hin; p.W = Win; p.Cin = cin; p.Cout = cout; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.ksz = k; p.pad = pad;
     p.border_cls = 0; p.splitk = 1; p.ksteps_per_split = k * k * (cin / 64) * (x2 ? 3 : 1); p.post_relu = post_relu ? 1 : 0;
     op.in_buf = in_buf; op.out_buf = out_buf; op.resid_buf = resid_buf;
+    op.unit = unit; op.role = role;
+    if (r->grad) {
+        // d(input) = conv(d(output), Wb) at stride 1 on the OUTPUT grid: Wb[ci][tap'][co] = Wfolded[co][k*k-1-tap'][ci], the
+        // values the forward multiplies by.  (A stride-2 1x1 reads only even positions: its result is scattered there.)
+        op.bvariant = direct_variant_tiles(k, 1, pad, Ho, Wo, cout, cin);
+        const int bcpl = op.bvariant ? direct_variant_cpl(op.bvariant) : 16;
+        const int KB = k * k * cout;
+        std::vector<uint16_t> wb((size_t)cin * KB);
+        for (int ci = 0; ci < cin; ++ci) {
+            const size_t row = (size_t)permuted_row(ci, bcpl) * KB;
+            for (int tap = 0; tap < k * k; ++tap) {
+                const int ft = k * k - 1 - tap;
+                for (int co = 0; co < cout; ++co) {
+                    const double v = a[co] * (double)w[((size_t)ft * cin + ci) * cout + co];
+                    const size_t kidx = op.bvariant ? ((size_t)(co >> 6) * 9 + tap) * 64 + (co & 63) : (size_t)tap * cout + co;
+                    wb[row + kidx] = cvt(r->dtype, (float)v);
+                }
+            }
+        }
+        if ((rc = upload(r, wb, &op.d_wb))) return rc;
+        if (role != 4) {                                   // the projection's output is not needed again
+            op.slot = (int)r->slot_elems.size();
+            r->slot_elems.push_back((size_t)Ho * Wo * cout);
+        }
+    }
     r->ops.push_back(op);
     r->buf_elems_per_image = std::max(r->buf_elems_per_image, (size_t)Ho * Wo * cout);
     return ALINK_OK;
@@ -601,11 +645,35 @@ int alink_resnet50_finalize(alink_resnet50_t* r) {
         if ((rc = upload(r, wq, &r->d_stem_w))) return rc;
         if ((rc = upload(r, bias, (void**)&r->d_stem_bias))) return rc;
     }
+    if (r->grad) {
+        const auto& w = r->raw.at("conv1/7x7_s2/kernel");
+        std::vector<double> a, b;
+        bn_fold(r, "conv1/7x7_s2", a, b);
+        // the stem backward's A fragments [tap][channel half][lane = (q, row c)][8] (resnet50_bwd.hip): row c < 3 holds the folded
+        // weights of channels 32 h + 8 q .., rows 3 .. 15 are zero
+        std::vector<uint16_t> wf((size_t)49 * 2 * 64 * 8, cvt(r->dtype, 0.f));
+        for (int tap = 0; tap < 49; ++tap)
+            for (int h = 0; h < 2; ++h)
+                for (int q = 0; q < 4; ++q)
+                    for (int c = 0; c < 3; ++c)
+                        for (int i = 0; i < 8; ++i) {
+                            const int co = 32 * h + 8 * q + i;
+                            const double v = a[co] * (double)w[((size_t)tap * 3 + c) * 64 + co];
+                            wf[((((size_t)tap * 2 + h) * 64) + 16 * q + c) * 8 + i] = cvt(r->dtype, (float)v);
+                        }
+        if ((rc = upload(r, wf, &r->d_stem_wfrag))) return rc;
+    }
     r->buf_elems_per_image = (size_t)r->Ho1 * r->Wo1 * 64;
     // ---- op list.  Buffers 0..3; stem -> 0, pool -> 1 (= x)
-    Op st; st.kind = 0; st.out_buf = 0; st.name = "conv1/7x7_s2"; r->ops.push_back(st);
-    Op mp; mp.kind = 1; mp.in_buf = 0; mp.out_buf = 1; mp.name = "max_pool"; r->ops.push_back(mp);
-    int x = 1, H = r->Hp, W = r->Wp, cin = 64;
+    Op st; st.kind = 0; st.out_buf = 0; st.name = "conv1/7x7_s2";
+    Op mp; mp.kind = 1; mp.in_buf = 0; mp.out_buf = 1; mp.name = "max_pool";
+    if (r->grad) {
+        st.slot = 0; mp.slot = 1;
+        r->slot_elems = {(size_t)r->Ho1 * r->Wo1 * 64, (size_t)r->Hp * r->Wp * 64};
+    }
+    r->ops.push_back(st);
+    r->ops.push_back(mp);
+    int x = 1, H = r->Hp, W = r->Wp, cin = 64, unit = 0;
     for (int s = 0; s < 4; ++s) {
         const int mid = kMid[s], out = 4 * mid;
         for (int u = 1; u <= kUnits[s]; ++u) {
@@ -614,15 +682,15 @@ int alink_resnet50_finalize(alink_resnet50_t* r) {
             for (int b = 0; b < 4; ++b) if (b != x) fr[nf++] = b;
             const int t1 = fr[0], t2 = fr[1], sb = fr[2];
             const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-            if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_reduce"), 1, stride, cin, mid, H, W, x, t1, -1, true, false))) return rc;
-            if ((rc = add_conv(r, unit_name(s + 2, u, "3x3"), 3, 1, mid, mid, Ho, Wo, t1, t2, -1, true, false))) return rc;
+            if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_reduce"), 1, stride, cin, mid, H, W, x, t1, -1, true, false, unit, 1))) return rc;
+            if ((rc = add_conv(r, unit_name(s + 2, u, "3x3"), 3, 1, mid, mid, Ho, Wo, t1, t2, -1, true, false, unit, 2))) return rc;
             int resid = x;
             if (u == 1) {
-                if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_proj"), 1, stride, cin, out, H, W, x, sb, -1, false, false))) return rc;
+                if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_proj"), 1, stride, cin, out, H, W, x, sb, -1, false, false, unit, 4))) return rc;
                 resid = sb;
             }
-            if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_increase"), 1, 1, mid, out, Ho, Wo, t2, t1, resid, false, true))) return rc;
-            x = t1; H = Ho; W = Wo; cin = out;
+            if ((rc = add_conv(r, unit_name(s + 2, u, "1x1_increase"), 1, 1, mid, out, Ho, Wo, t2, t1, resid, false, true, unit, 3))) return rc;
+            x = t1; H = Ho; W = Wo; cin = out; ++unit;
         }
     }
     Op ap; ap.kind = 3; ap.in_buf = x; ap.name = "avg_pool"; r->ops.push_back(ap);
@@ -639,12 +707,27 @@ size_t alink_resnet50_workspace_bytes(const alink_resnet50_t* r, int n_images) {
 
 // calib (split precision only): 0 = a forward; 1 = choose every tensor's scale exponent from this batch; 2 = the same, never
 // above the exponents already held.  Synchronous when != 0.  (The scheme is csrc/backbone.hip's: embed_impl, settle.)
+static void r50_grad_layout(const alink_resnet50* r, int n, R50GradLayout* L) {
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t o = 0;
+    L->slot.assign(r->slot_elems.size(), 0);
+    for (size_t i = 0; i < r->slot_elems.size(); ++i) { L->slot[i] = o; o += al((size_t)n * r->slot_elems[i] * 2); }
+    const size_t big = al((size_t)n * r->buf_elems_per_image * 2);
+    L->scratch = o; o += big;
+    for (int i = 0; i < 4; ++i) { L->g[i] = o; o += big; }
+    L->scale = o; o += 256;
+    L->total = o;
+}
+
+// GL != nullptr: the cached forward — the same launches, every kept output written to its own slot of the activation cache
+// instead of one of the four rotating buffers (the kernels see other addresses, nothing else: bit-identical results)
 static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
-                   size_t ws_bytes, hipStream_t st, float* ms, double* flops, int* n_ops, int calib = 0) {
+                   size_t ws_bytes, hipStream_t st, float* ms, double* flops, int* n_ops, int calib = 0,
+                   const R50GradLayout* GL = nullptr) {
     ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_resnet50_embed before finalize");
     ALINK_REQUIRE(dev_in && dev_out && ws && n > 0, ALINK_EINVAL, "bad argument");
     ALINK_REQUIRE(((uintptr_t)ws & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
-    ALINK_REQUIRE(ws_bytes >= alink_resnet50_workspace_bytes(r, n), ALINK_ENOMEM, "workspace too small");
+    ALINK_REQUIRE(ws_bytes >= (GL ? GL->total : alink_resnet50_workspace_bytes(r, n)), ALINK_ENOMEM, "workspace too small");
     const bool x2 = r->dtype == ALINK_DT_F16X2;
     ALINK_REQUIRE((long long)n * r->buf_elems_per_image * (x2 ? 2 : 1) < (1ll << 31), ALINK_EINVAL, "batch of %d too large; split it", n);
     ALINK_REQUIRE(!calib || x2, ALINK_ESTATE, "only the split-precision mode is calibrated");
@@ -674,7 +757,9 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
         *e_io = e;
         return ALINK_OK;
     };
-    auto buf = [&](int id) -> void* { return (char*)ws + one * id; };
+    void* bptr[4];
+    for (int i = 0; i < 4; ++i) bptr[i] = GL ? nullptr : (void*)((char*)ws + one * i);
+    auto buf = [&](int id) -> void* { return bptr[id]; };
     const bool prof = ms != nullptr;
     std::vector<hipEvent_t> ev;
     auto mark = [&]() -> int {
@@ -689,6 +774,7 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
     if ((rc = mark())) return rc;
     for (Op& op : r->ops) {
         double fl = 0.0;
+        if (GL && op.out_buf >= 0) bptr[op.out_buf] = (char*)ws + (op.slot >= 0 ? GL->slot[op.slot] : GL->scratch);
         if (op.kind == 0) {
             Stem7Params p{};
             p.in = dev_in; p.wgt = r->d_stem_w; p.bias = r->d_stem_bias; p.out = buf(op.out_buf);
@@ -841,6 +927,139 @@ int alink_resnet50_embed(alink_resnet50_t* r, const float* dev_in, int n_images,
     DeviceGuard dg(r->device);
     return r50_run(r, dev_in, n_images, preprocessed, dev_out, dev_workspace, workspace_bytes, (hipStream_t)stream,
                    nullptr, nullptr, nullptr);
+}
+
+// ---- input gradient (FGSM / PGD extension) ------------------------------------------------------------
+int alink_resnet50_enable_grad(alink_resnet50_t* r) {
+    ALINK_REQUIRE(r, ALINK_EINVAL, "NULL network");
+    ALINK_REQUIRE(!r->finalized, ALINK_ESTATE, "alink_resnet50_enable_grad must precede alink_resnet50_finalize");
+    ALINK_REQUIRE(r->dtype == ALINK_DT_BF16 || r->dtype == ALINK_DT_F16, ALINK_ESTATE,
+                  "the split-precision mode (ALINK_DT_F16X2) has no gradient pass: use ALINK_DT_BF16 or ALINK_DT_F16");
+    r->grad = true;
+    return ALINK_OK;
+}
+
+size_t alink_resnet50_grad_workspace_bytes(const alink_resnet50_t* r, int n_images) {
+    if (!r || !r->finalized || !r->grad || n_images <= 0) return 0;
+    R50GradLayout L;
+    r50_grad_layout(r, n_images, &L);
+    return L.total;
+}
+
+int alink_resnet50_embed_cached(alink_resnet50_t* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,
+                                void* dev_workspace, size_t workspace_bytes, void* stream) {
+    ALINK_REQUIRE(r && r->finalized && r->grad, ALINK_ESTATE, "needs alink_resnet50_enable_grad + finalize");
+    DeviceGuard dg(r->device);
+    R50GradLayout L;
+    r50_grad_layout(r, n_images > 0 ? n_images : 1, &L);
+    return r50_run(r, dev_in, n_images, preprocessed, dev_out, dev_workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr,
+                   nullptr, 0, &L);
+}
+
+// ms != nullptr: HIP events around the stages — [0] scale + average pool, [1 .. 16] the units from conv5_3 down to conv2_1,
+// [17] max-pool, [18] stem — and a synchronise at the end
+static int r50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_images, int preprocessed, float* dev_dpix,
+                          void* dev_workspace, size_t workspace_bytes, void* stream, float* ms, int* n_stages) {
+    ALINK_REQUIRE(r && r->finalized && r->grad, ALINK_ESTATE, "needs alink_resnet50_enable_grad + finalize");
+    DeviceGuard dg(r->device);
+    std::vector<hipEvent_t> ev;
+    struct Drop { std::vector<hipEvent_t>& v; ~Drop() { for (hipEvent_t e : v) (void)hipEventDestroy(e); } } drop{ev};
+    auto mark = [&]() -> int {
+        if (!ms) return ALINK_OK;
+        hipEvent_t e;
+        ALINK_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+        ALINK_HIP(hipEventRecord(e, (hipStream_t)stream));
+        return ALINK_OK;
+    };
+    const int N = n_images, dt = r->dtype;
+    ALINK_REQUIRE(dev_dfeat && dev_dpix && dev_workspace && N > 0, ALINK_EINVAL, "bad argument");
+    ALINK_REQUIRE(((uintptr_t)dev_workspace & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
+    ALINK_REQUIRE((long long)N * r->buf_elems_per_image < (1ll << 31), ALINK_EINVAL, "batch of %d too large; split it", N);
+    hipStream_t st = (hipStream_t)stream;
+    R50GradLayout GL;
+    r50_grad_layout(r, N, &GL);
+    ALINK_REQUIRE(workspace_bytes >= GL.total, ALINK_ENOMEM, "workspace too small: %zu < %zu", workspace_bytes, GL.total);
+    char* base = (char*)dev_workspace;
+    auto G = [&](int i) -> void* { return base + GL.g[i]; };
+    auto cache = [&](const Op& op) -> const void* { return base + GL.slot[op.slot]; };
+    float* scale = (float*)(base + GL.scale);
+    // the ops of every unit
+    const int n_units = kUnits[0] + kUnits[1] + kUnits[2] + kUnits[3];
+    std::vector<const Op*> red(n_units, nullptr), c33(n_units, nullptr), inc(n_units, nullptr), prj(n_units, nullptr);
+    for (const Op& op : r->ops)
+        if (op.kind == 2) (op.role == 1 ? red : (op.role == 2 ? c33 : (op.role == 3 ? inc : prj)))[op.unit] = &op;
+    // 1) the call's scale, 2) through the average pool and the last unit's ReLU
+    const int HWf = r->Hf * r->Wf;
+    int rc;
+    if ((rc = mark())) return rc;
+    ALINK_HIP(launch_r50_grad_scale(dev_dfeat, N * 2048, HWf, scale, st));
+    int cur = 0;
+    ALINK_HIP(launch_r50_avgpool_bwd(dt, dev_dfeat, cache(*inc[n_units - 1]), G(cur), scale, N, HWf, 2048, st));
+    // 3) bottleneck units in reverse.  G(cur) = d(loss)/d(z), z = the unit's sum before its final ReLU
+    auto conv = [&](const Op& op, const void* in, const void* dact, const void* resid, void* out) -> int {
+        const ConvParams& f = op.cp;                // backward of f: Cout -> Cin on f's output grid, stride 1
+        ConvParams p{};
+        p.in = in; p.wgt = op.d_wb; p.bias = r->d_zero_alpha; p.alpha = dact ? r->d_zero_alpha : nullptr; p.dact = dact;
+        p.resid = resid; p.out = out; p.zero = r->d_zero;
+        p.N = N; p.H = f.Ho; p.W = f.Wo; p.Cin = f.Cout; p.Cout = f.Cin; p.Ho = f.Ho; p.Wo = f.Wo; p.stride = 1; p.ksz = f.ksz;
+        p.pad = f.pad; p.M = N * f.Ho * f.Wo; p.splitk = 1; p.ksteps_per_split = f.ksz * f.ksz * (f.Cout / 64);
+        if (op.bvariant) ALINK_HIP(launch_conv3x3_direct(op.bvariant, dt, p, st));
+        else             ALINK_HIP(launch_conv_igemm(dt, p, st));
+        return ALINK_OK;
+    };
+    for (int u = n_units - 1; u >= 0; --u) {
+        if ((rc = mark())) return rc;
+        const Op &A = *red[u], &B = *c33[u], &C3 = *inc[u];
+        int ids[3], k = 0;
+        for (int i = 0; i < 4; ++i) if (i != cur) ids[k++] = i;
+        // through 1x1_increase and the 3x3's ReLU, then through the 3x3 and 1x1_reduce's ReLU
+        if ((rc = conv(C3, G(cur), cache(B), nullptr, G(ids[0])))) return rc;
+        if ((rc = conv(B, G(ids[0]), cache(A), nullptr, G(ids[1])))) return rc;
+        // the shortcut's gradient: d(z) itself, or through the transposed projection; added in 1x1_reduce's epilogue
+        const void* sc = G(cur);
+        if (prj[u]) {
+            if ((rc = conv(*prj[u], G(cur), nullptr, nullptr, G(ids[0])))) return rc;
+            sc = G(ids[0]);
+        }
+        if ((rc = conv(A, G(ids[1]), nullptr, sc, G(ids[2])))) return rc;
+        // d(unit input) -> d(z) of the unit before: that unit's ReLU mask (the first unit reads the max-pool: no mask)
+        const ConvParams& f = A.cp;
+        if (f.stride == 2) {
+            ALINK_REQUIRE(u > 0, ALINK_ESTATE, "a strided first unit");
+            ALINK_HIP(launch_r50_scatter_mask(dt, G(ids[2]), cache(*inc[u - 1]), G(cur), N, f.H, f.W, f.Ho, f.Wo, f.Cin, st));
+        } else {
+            if (u > 0) ALINK_HIP(launch_r50_relu_mask(dt, G(ids[2]), cache(*inc[u - 1]), (long long)N * f.H * f.W * f.Cin, st));
+            cur = ids[2];
+        }
+    }
+    // 4) through the max-pool and the stem's ReLU, 5) through the stem convolution (the mean subtraction has derivative 1)
+    int nx = (cur + 1) & 3;
+    if ((rc = mark())) return rc;
+    ALINK_HIP(launch_r50_maxpool_bwd(dt, base + GL.slot[0], base + GL.slot[1], G(cur), G(nx), N, r->Ho1, r->Wo1, 64, r->Hp, r->Wp, st));
+    const int th = std::max((r->Ho1 - 1) * 2 + 7 - r->H, 0), tw = std::max((r->Wo1 - 1) * 2 + 7 - r->W, 0);
+    if ((rc = mark())) return rc;
+    ALINK_HIP(launch_r50_stem_bwd(dt, G(nx), r->d_stem_wfrag, dev_dpix, scale, N, r->H, r->W, r->Ho1, r->Wo1, th / 2, tw / 2,
+                                  preprocessed ? 0 : 1, st));
+    if ((rc = mark())) return rc;
+    if (ms) {
+        ALINK_HIP(hipStreamSynchronize(st));
+        int k = 0;
+        for (; k + 1 < (int)ev.size() && k < *n_stages; ++k) ALINK_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+        *n_stages = k;
+    }
+    return ALINK_OK;
+}
+
+int alink_resnet50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_images, int preprocessed, float* dev_dpix,
+                              void* dev_workspace, size_t workspace_bytes, void* stream) {
+    return r50_input_grad(r, dev_dfeat, n_images, preprocessed, dev_dpix, dev_workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+int alink_resnet50_input_grad_profile(alink_resnet50_t* r, const float* dev_dfeat, int n_images, int preprocessed, float* dev_dpix,
+                                      void* dev_workspace, size_t workspace_bytes, void* stream, float* ms, int* n_stages) {
+    ALINK_REQUIRE(ms && n_stages && *n_stages > 0, ALINK_EINVAL, "NULL profile buffers");
+    return r50_input_grad(r, dev_dfeat, n_images, preprocessed, dev_dpix, dev_workspace, workspace_bytes, stream, ms, n_stages);
 }
 
 int alink_resnet50_profile(alink_resnet50_t* r, const float* dev_in, int n_images, float* dev_out, void* dev_workspace,

@@ -307,8 +307,9 @@ class FGSM(Noise):
         x' = clip(x -/+ eps * sign(d BCE(scorer(f(xl), f(xr)), target) / dx), 0, 255)
     targeted (default, like PixelAttacker.attack_all: target class = argmax(target_labels[i])) steps
     DOWN the loss of the target class; untargeted steps UP the loss of the given labels.
-    Needs an ArcFace-style feature model built with gradients (`ArcFace(..., enable_grad=True)`) and a
-    DenseHead-backed pair model."""
+    Needs a feature model that offers a gradient backbone — `ArcFace(..., grad_dtype=...)` / `RESNET50(..., grad_dtype=...)`
+    (`feature_model.grad_backbone`), or `ArcFace(..., enable_grad=True)` (its own backbone) — and a DenseHead-backed pair
+    model.  The attack runs wholly on that backbone: max_batch, embed_device, embed_with_cache, input_gradient."""
     steps, alpha, random_start = 1, None, False
 
     def __init__(self, model=None, sess=None, feature_model=None, eps=4.0, targeted=True, clip=(0.0, 255.0),
@@ -318,10 +319,13 @@ class FGSM(Noise):
 
     def _parts(self):
         from .head import DenseHead
-        bb = getattr(getattr(self.feature_model, "model", None), "model", None)
+        bb = getattr(self.feature_model, "grad_backbone", None)
+        if bb is None:
+            bb = getattr(getattr(self.feature_model, "model", None), "model", None)
         head = getattr(self.model, "siamese_net", None)
         if bb is None or not getattr(bb, "grad_enabled", False) or not isinstance(head, DenseHead):
-            raise TypeError("FGSM/PGD need ArcFace(..., enable_grad=True) and a DenseHead-backed pair model")
+            raise TypeError("FGSM/PGD need a feature model with a gradient backbone (ArcFace / RESNET50 built with grad_dtype=..., "
+                            "or ArcFace(..., enable_grad=True)) and a DenseHead-backed pair model")
         return bb, head
 
     def _targets(self, target_labels, n, out_dim):

@@ -82,7 +82,7 @@ def save_keras_h5(path, params):
 
 class VGGResNet50(object):
     def __init__(self, image_size=(224, 224), weights=None, dtype="bf16", device=None, max_batch=128, bn_eps=1e-3,
-                 seed=1):
+                 seed=1, enable_grad=False):
         import torch
         self.torch = torch
         if not torch.cuda.is_available():
@@ -101,12 +101,17 @@ class VGGResNet50(object):
         # dtype "f16x2": split precision (f16 pairs, three products on the f16 matrix cores, calibrated power-of-two scales:
         # a-link_amd/backbone.py) — features to float32 accuracy, what selection through this feature model needs
         self.dtype = dtype
+        # enable_grad: the input-gradient pass (FGSM / PGD extension; 16-bit modes only): embed_with_cache / input_gradient
+        self.grad_enabled = bool(enable_grad)
+        self._grad_ws, self._cached = None, None
         with _abi.on_device(device):
             self.h = self.lib.alink_resnet50_create(int(image_size[0]), int(image_size[1]),
                                                     {"bf16": _abi.DT_BF16, "f16": _abi.DT_F16, "f16x2": _abi.DT_F16X2}[dtype],
                                                     float(bn_eps))
         if not self.h:
             raise _abi.AlinkError("alink_resnet50_create: " + self.lib.alink_last_error().decode())
+        if enable_grad:
+            _abi.check(self.lib.alink_resnet50_enable_grad(self.h), "alink_resnet50_enable_grad")
         name, cnt = C.c_char_p(), C.c_size_t()
         for i in range(self.lib.alink_resnet50_num_tensors(self.h)):
             _abi.check(self.lib.alink_resnet50_tensor_info(self.h, i, C.byref(name), C.byref(cnt)))
@@ -196,6 +201,59 @@ class VGGResNet50(object):
                     return self.embed_device(x, preprocessed, out=out, _retry=False)
                 raise _abi.AlinkError("activations exceeded the float16 range in this network: use dtype='bf16' or 'f16x2'")
         return out
+
+    # -- input gradient (FGSM / PGD extension) --------------------------------------------------------
+    def _grad_workspace(self, n):
+        cur = self._grad_ws
+        if cur is None or n > cur[1]:
+            nbytes = self.lib.alink_resnet50_grad_workspace_bytes(self.h, n)
+            self._grad_ws = cur = None                 # release the smaller one first: the cache is ~18 MB per image
+            cur = (self.torch.empty(nbytes + 256, dtype=self.torch.uint8, device="cuda:%d" % self.device), n)
+            self._grad_ws = cur
+        t = cur[0]
+        off = (-t.data_ptr()) % 256
+        return t.data_ptr() + off, t.numel() - off
+
+    def embed_with_cache(self, x, preprocessed=False):
+        """Forward on <= max_batch images keeping what input_gradient needs: embed_device's features, bit for bit.
+        x: CUDA (n, H, W, 3) float32, raw RGB or (preprocessed=True) preprocess()'d."""
+        if not self.grad_enabled:
+            raise _abi.AlinkError("VGGResNet50 was built without enable_grad=True")
+        torch = self.torch
+        if x.ndim != 4 or tuple(x.shape[1:]) != self.image_size + (3,):
+            raise ValueError("expected images of shape (N,%d,%d,3), got %s" % (self.image_size + (tuple(x.shape),)))
+        if x.dtype != torch.float32:
+            raise ValueError("gradients need float32 pixels")
+        x = x.contiguous()
+        n = x.shape[0]
+        assert 0 < n <= self.max_batch
+        out = torch.empty((n, 2048), dtype=torch.float32, device=x.device)
+        ws, wsb = self._grad_workspace(n)
+        _abi.check(self.lib.alink_resnet50_embed_cached(self.h, _abi.ptr(x), n, 1 if preprocessed else 0, _abi.ptr(out),
+                                                        C.c_void_p(ws), wsb, _abi.current_stream(self.device)),
+                   "alink_resnet50_embed_cached")
+        self._cached = (n, bool(preprocessed))
+        if self.dtype == "f16":
+            torch.cuda.synchronize(self.device)
+            if self.lib.alink_resnet50_range_flag(self.h, 1):
+                raise _abi.AlinkError("activations exceeded the float16 range in this network: use dtype='bf16'")
+        return out
+
+    def input_gradient(self, dfeat):
+        """d(loss)/d(pixels) for the batch of the last embed_with_cache, given dfeat = d(loss)/d(feature), (n, 2048) float32
+        CUDA.  (n, H, W, 3) float32 in the channel order of that forward's input (raw RGB unless it was preprocessed)."""
+        torch = self.torch
+        if self._cached is None:
+            raise _abi.AlinkError("input_gradient before embed_with_cache")
+        n, preprocessed = self._cached
+        dfeat = dfeat.to(torch.float32).contiguous()
+        assert tuple(dfeat.shape) == (n, 2048)
+        dpix = torch.empty((n,) + self.image_size + (3,), dtype=torch.float32, device=dfeat.device)
+        ws, wsb = self._grad_workspace(n)
+        _abi.check(self.lib.alink_resnet50_input_grad(self.h, _abi.ptr(dfeat), n, 1 if preprocessed else 0, _abi.ptr(dpix),
+                                                      C.c_void_p(ws), wsb, _abi.current_stream(self.device)),
+                   "alink_resnet50_input_grad")
+        return dpix
 
     def predict(self, X, batch_size=128, verbose=0, preprocessed=True):
         """Keras Model.predict on PREPROCESSED input (what RESNET50.process passes, code/siamese.py:216)."""

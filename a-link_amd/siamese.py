@@ -390,7 +390,7 @@ class RESNET50:
     the keras-vggface weight file (`rcmalli_vggface_tf_notop_resnet50.h5`), a dict, or None for
     synthetic weights (keras-vggface downloads its file; there is no network here)."""
 
-    def __init__(self, shape, weights=None, dtype=None, max_batch=128, seed=1, screen_dtype=None):
+    def __init__(self, shape, weights=None, dtype=None, max_batch=128, seed=1, screen_dtype=None, grad_dtype=None):
         from .resnet50 import VGGResNet50
         self.shape = shape + (3,)
         # dtype=None: "f16x2", split precision — features to float32 accuracy, so that the selection the drivers make from
@@ -403,6 +403,12 @@ class RESNET50:
         if screen_dtype:
             self.screen = VGGResNet50(image_size=tuple(shape), weights=weights, dtype=screen_dtype, max_batch=max_batch, seed=seed)
             self.process_screen = self._process_screen
+
+        # grad_dtype ("bf16" | "f16"): a further handle on the same weights with the input-gradient pass, for the FGSM / PGD noise
+        # (noise.FGSM reads `grad_backbone`); process() and every other result stay the exact mode's.  Not in the reference.
+        if grad_dtype:
+            self.grad_backbone = VGGResNet50(image_size=tuple(shape), weights=weights, dtype=grad_dtype, max_batch=max_batch, seed=seed,
+                                             enable_grad=True)
 
     def _process_screen(self, X):
         if isinstance(X, (list, tuple)):
@@ -429,7 +435,7 @@ class RESNET50:
 
 class ArcFace:
     def __init__(self, shape, model_path, dtype=None, max_batch=292, enable_grad=False, small_batch_split=False,
-                 gpu=None, screen_dtype="default"):
+                 gpu=None, screen_dtype="default", grad_dtype=None):
         # dtype=None: face_model.default_dtype — "f16x2" (selection sets identical to the reference's float32
         # arithmetic), or "bf16" when the gradient pass is requested
         args = _Args({
@@ -454,6 +460,10 @@ class ArcFace:
         # framework loop just reaches them ~2x sooner; None / False builds no screening form.
         # The screening handle is built LAZILY, on the first process_screen / backbones() / .screen access: a caller that
         # only ever calls process() (the reference's API) pays for one network, not two.
+        # grad_dtype ("bf16" | "f16"): a further handle on the same checkpoint with the input-gradient pass, for the FGSM / PGD
+        # noise (noise.FGSM reads `grad_backbone`); `process` and every other result stay this model's.  Not in the reference.
+        if grad_dtype:
+            self.grad_backbone = face_model.FaceModel(_Args(dict(args, dtype=grad_dtype, enable_grad=True))).model
         if screen_dtype == "default":
             screen_dtype = "auto" if (self.model.model.dtype == "f16x2" and not enable_grad) else None
         self._screen_dtype, self._screen_args, self._screen = (screen_dtype or None), args, None

@@ -222,6 +222,25 @@ int alink_resnet50_range_flag(alink_resnet50_t* r, int reset);
 int alink_resnet50_num_scales(const alink_resnet50_t* r);
 int alink_resnet50_get_scales(const alink_resnet50_t* r, int* exponents, int n);
 int alink_resnet50_set_scales(alink_resnet50_t* r, const int* exponents, int n);
+/* EXTENSION, as alink_backbone_enable_grad and its three companions above: d(loss)/d(pixels) through the frozen network for
+ * FGSM / PGD, 16-bit modes only (ALINK_DT_F16X2: ALINK_ESTATE).  alink_resnet50_enable_grad (before finalize) also builds the
+ * transposed, flipped folded weights (doubles weight memory).  alink_resnet50_embed_cached = alink_resnet50_embed, bit for
+ * bit, that keeps every activation the backward pass needs in the (larger) workspace: about 9.1 M 16-bit elements per
+ * 224 x 224 image.  alink_resnet50_input_grad then maps dev_dfeat = d(loss)/d(feature) (n x 2048 float32) of that forward to
+ * dev_dpix = d(loss)/d(pixel) (n x H x W x 3 float32, in the channel order of the forward's input: with preprocessed = 0 the
+ * gradient with respect to the raw RGB pixels).  Same n, preprocessed and workspace as the cached forward; the gradient
+ * tensors are scaled by a power of two per call (max|dev_dfeat|), so small gradients do not underflow in ALINK_DT_F16. */
+int alink_resnet50_enable_grad(alink_resnet50_t* r);
+size_t alink_resnet50_grad_workspace_bytes(const alink_resnet50_t* r, int n_images);
+int alink_resnet50_embed_cached(alink_resnet50_t* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,
+                                void* dev_workspace, size_t workspace_bytes, void* stream);
+int alink_resnet50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_images, int preprocessed, float* dev_dpix,
+                              void* dev_workspace, size_t workspace_bytes, void* stream);
+/* alink_resnet50_input_grad with HIP events around its stages (synchronous): ms[0] gradient scale + average pool, ms[1 .. 16] the
+ * bottleneck units from conv5_3 down to conv2_1, ms[17] max-pool, ms[18] stem.  *n_stages in: capacity, out: count. */
+int alink_resnet50_input_grad_profile(alink_resnet50_t* r, const float* dev_dfeat, int n_images, int preprocessed,
+                                      float* dev_dpix, void* dev_workspace, size_t workspace_bytes, void* stream, float* ms,
+                                      int* n_stages);
 /* per-op HIP-event timing of one forward (synchronous): ms[i] / flops[i] for op i, name via op_name */
 int alink_resnet50_profile(alink_resnet50_t* r, const float* dev_in, int n_images, float* dev_out,
                            void* dev_workspace, size_t workspace_bytes, void* stream, float* ms,

@@ -216,6 +216,7 @@ hipError_t launch_r50_maxpool_bwd(int dtype, const void* y0, const void* pooled,
                                   int Hp, int Wp, hipStream_t st);
 hipError_t launch_r50_stem_bwd(int dtype, const void* d0, const void* wfrag, float* dpix, const float* scale, int N, int H, int W,
                                int Ho, int Wo, int pad_t, int pad_l, int flip, hipStream_t st);
+int r50_stem_bwd_max_width();      // widest image launch_r50_stem_bwd takes (its rows are 16-pixel tiles per parity class)
 
 // host-side conversions
 uint16_t f32_to_bf16_rne(float f);

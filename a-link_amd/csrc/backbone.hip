@@ -1209,6 +1209,35 @@ size_t alink_backbone_grad_workspace_bytes(const alink_backbone_t* bb, int n_ima
     return L.total;
 }
 
+// diagnostic (include/alink_hip_debug.h): where the cached forward keeps what alink_embed_input_grad reads besides its
+// arguments: the stem's PReLU output, every unit's conv1 PReLU output, and the float32 row norms.  Computed from ws_layout /
+// grad_layout; launches nothing.
+int alink_debug_backbone_grad_cache_info(const alink_backbone_t* bb, int n_images, int index, size_t* byte_offset, int* H, int* W,
+                                         int* C, char* name_buf, int name_len) {
+    if (!bb || !bb->finalized || !bb->grad || n_images <= 0) { set_error("needs alink_backbone_enable_grad + finalize and n_images > 0"); return -1; }
+    const int count = bb->n_units + 2;
+    if (index < 0) return count;
+    if (index >= count) { set_error("cache entry %d of %d", index, count); return -1; }
+    GradLayout L;
+    grad_layout(bb, n_images, &L);
+    size_t off[7], total, o;
+    ws_layout(bb, n_images, off, &total);
+    int h = 1, w = 1, c = 1;
+    std::string name = "norms";
+    if (index == 0) { o = off[0]; h = bb->cfg.height; w = bb->cfg.width; c = bb->cfg.widths[0]; name = "stem"; }
+    else if (index <= bb->n_units) {
+        o = L.toff[index - 1];
+        for (const ConvLayer& l : bb->convs)
+            if (l.role == 1 && l.unit == index - 1) { h = l.Hout; w = l.Wout; c = l.Cout; name = l.name; }
+    } else o = L.norms;
+    if (byte_offset) *byte_offset = o;
+    if (H) *H = h;
+    if (W) *W = w;
+    if (C) *C = c;
+    if (name_buf && name_len > 0) snprintf(name_buf, (size_t)name_len, "%s", name.c_str());
+    return count;
+}
+
 int alink_embed_cached(alink_backbone_t* bb, const void* dev_in, int layout, int n_images, float* dev_out,
                        void* dev_workspace, size_t workspace_bytes, void* stream) {
     ALINK_REQUIRE(bb && bb->finalized && bb->grad, ALINK_ESTATE, "needs alink_backbone_enable_grad + finalize");

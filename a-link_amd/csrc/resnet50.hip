@@ -935,6 +935,11 @@ int alink_resnet50_enable_grad(alink_resnet50_t* r) {
     ALINK_REQUIRE(!r->finalized, ALINK_ESTATE, "alink_resnet50_enable_grad must precede alink_resnet50_finalize");
     ALINK_REQUIRE(r->dtype == ALINK_DT_BF16 || r->dtype == ALINK_DT_F16, ALINK_ESTATE,
                   "the split-precision mode (ALINK_DT_F16X2) has no gradient pass: use ALINK_DT_BF16 or ALINK_DT_F16");
+    // the stem backward walks a row of one pixel parity as a fixed number of 16-pixel tiles (resnet50_bwd.hip): widths the forward
+    // takes beyond that (225 .. 228) are refused here, in words, not by the launch at the end of a whole backward pass
+    ALINK_REQUIRE(r->W <= r50_stem_bwd_max_width(), ALINK_EINVAL,
+                  "the input-gradient pass takes images up to %d pixels wide (its stem kernel's row tiles), got %d x %d",
+                  r50_stem_bwd_max_width(), r->H, r->W);
     r->grad = true;
     return ALINK_OK;
 }
@@ -944,6 +949,33 @@ size_t alink_resnet50_grad_workspace_bytes(const alink_resnet50_t* r, int n_imag
     R50GradLayout L;
     r50_grad_layout(r, n_images, &L);
     return L.total;
+}
+
+// diagnostic (include/alink_hip_debug.h): where the cached forward keeps the tensors the backward takes a ReLU mask or a
+// max-pool winner from, in the caller's gradient workspace.  Computed from r50_grad_layout; launches nothing.
+int alink_debug_resnet50_grad_cache_info(const alink_resnet50_t* r, int n_images, int index, size_t* byte_offset, int* H, int* W,
+                                         int* C, char* name_buf, int name_len) {
+    if (!r || !r->finalized || !r->grad || n_images <= 0) { set_error("needs alink_resnet50_enable_grad + finalize and n_images > 0"); return -1; }
+    struct Entry { int slot, H, W, C; std::string name; };
+    std::vector<Entry> es;
+    es.push_back({0, r->Ho1, r->Wo1, 64, "stem"});
+    es.push_back({1, r->Hp, r->Wp, 64, "pool"});
+    for (const Op& op : r->ops) {
+        if (op.kind != 2 || op.slot < 0) continue;
+        const char* what = op.role == 1 ? "reduce" : (op.role == 2 ? "3x3" : "out");
+        es.push_back({op.slot, op.cp.Ho, op.cp.Wo, op.cp.Cout, op.name.substr(0, op.name.find('_', 6) + 1) + what});
+    }
+    if (index < 0) return (int)es.size();
+    if (index >= (int)es.size()) { set_error("cache entry %d of %d", index, (int)es.size()); return -1; }
+    R50GradLayout L;
+    r50_grad_layout(r, n_images, &L);
+    const Entry& e = es[index];
+    if (byte_offset) *byte_offset = L.slot[e.slot];
+    if (H) *H = e.H;
+    if (W) *W = e.W;
+    if (C) *C = e.C;
+    if (name_buf && name_len > 0) snprintf(name_buf, (size_t)name_len, "%s", e.name.c_str());
+    return (int)es.size();
 }
 
 int alink_resnet50_embed_cached(alink_resnet50_t* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,

@@ -290,6 +290,8 @@ hipError_t launch_r50_maxpool_bwd(int dtype, const void* y0, const void* pooled,
     return hipGetLastError();
 }
 
+int r50_stem_bwd_max_width() { return 2 * 16 * SB_TILES; }
+
 hipError_t launch_r50_stem_bwd(int dtype, const void* d0, const void* wfrag, float* dpix, const float* scale, int N, int H, int W,
                                int Ho, int Wo, int pad_t, int pad_l, int flip, hipStream_t st) {
     const long long rows = (long long)N * ((H + 1) / 2);

@@ -14,6 +14,8 @@
 #ifndef ALINK_HIP_DEBUG_H
 #define ALINK_HIP_DEBUG_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -83,6 +85,25 @@ void alink_debug_set_stamps(void* dev_u64);
 int alink_debug_lds_oob_probe(float* dev_out516, void* stream);
 /* 1 if that probe passed on the current device at alink_init (the linear-tile kernel is used only then) */
 int alink_debug_linear_contract_ok(void);
+
+
+/* ---- what the input-gradient passes read from the caller's workspace (read-only queries: nothing is launched or changed) - */
+/* The cached forwards (alink_resnet50_embed_cached, alink_embed_cached) keep activations in the gradient workspace the caller
+ * owns; the backward takes its ReLU / PReLU masks and max-pool winners from them.  These tell a test where they are, so that
+ * a reference can use the SAME masks (tests/test_gpu_grad_masked.py).  Entry `index` of the layout for n_images images: byte
+ * offset from the (256-byte aligned) workspace pointer, shape [n_images][H][W][C] in the network's 16-bit type, and a name.
+ * Return the number of entries (also for index < 0, which fills nothing), or -1 with alink_last_error set.  Any out pointer
+ * may be NULL.
+ *   ResNet-50: "stem" (conv1/7x7_s2 after ReLU), "pool" (max-pool output), then per unit "convS_U_reduce", "convS_U_3x3"
+ *   (after ReLU) and "convS_U_out" (the unit's output, after the ReLU of the sum).
+ *   IR backbone: "stem" (after PReLU), per unit "stageS_unitU_conv1" (after PReLU), and last "norms": FLOAT32 [n_images]
+ *   (H = W = C = 1), the row norms the L2 normalisation divided by. */
+struct alink_resnet50;
+struct alink_backbone;
+int alink_debug_resnet50_grad_cache_info(const struct alink_resnet50* r, int n_images, int index, size_t* byte_offset, int* H,
+                                         int* W, int* C, char* name_buf, int name_len);
+int alink_debug_backbone_grad_cache_info(const struct alink_backbone* bb, int n_images, int index, size_t* byte_offset, int* H,
+                                         int* W, int* C, char* name_buf, int name_len);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/alink_hip.h"
+#include "conv_kernel.h"
 
 namespace alink {
 
@@ -67,7 +68,7 @@ typedef __attribute__((ext_vector_type(16))) float   f32x16;
 // ---- implicit-GEMM convolution launch descriptor -------------------------------------------------
 // Activations are NHWC in T (bf16 | f16); weights are [Cout][ksz*ksz*Cin] in T with the rows of
 // every 64-row block permuted by `perm64` (see conv_igemm.hip) so that a lane's 16 accumulator
-// values are 16 consecutive output channels.
+// values are 16 consecutive output channels.  The other kernels' orders: WeightLayout in conv_kernel.h.
 struct ConvParams {
     const void*  in;      // [N][H][W][Cin]
     const void*  wgt;     // [Cout][K]  (row-permuted)
@@ -137,40 +138,25 @@ hipError_t launch_absmax_f16(const void* x, size_t n_elements, unsigned* out_bit
 // epilogue of a split-K convolution: p as for the fused launch (out = the real output), slabs [S][M][Cout] f32
 hipError_t launch_conv_split_finish(int dtype, const ConvParams& p, const float* slabs, int S, hipStream_t stream);
 
-// position of natural channel c (0..63 within its 64-block) in the permuted weight rows
-static inline int perm64_row_of_channel(int c) {
-    // MFMA tile t (0..3), row 4q+j  <->  channel 16q + 4t + j
-    int q = c >> 4, t = (c >> 2) & 3, j = c & 3;
-    return 16 * t + 4 * q + j;
-}
-// same for kernels whose waves own 32 channels (2 MFMA tiles): tile t (0..1), row 4q+j <-> 8q + 4t + j
-static inline int perm32_row_of_channel(int c) {
-    int q = c >> 3, t = (c >> 2) & 1, j = c & 3;
-    return 16 * t + 4 * q + j;
-}
-// conv3x3_direct with 4 MFMA tiles per wave: tile t = 2 th + tl, row 4q+j  <->  channel 32 th + 8q + 4 tl + j,
-// i.e. a lane holds two runs of 8 consecutive channels, 32 apart
-static inline int perm64b_row_of_channel(int c) {
-    int th = c >> 5, q = (c >> 3) & 3, tl = (c >> 2) & 1, j = c & 3;
-    return 16 * (2 * th + tl) + 4 * q + j;
-}
-// weight row of output channel co; cpl: 16 = perm64 (conv_igemm, stems), 17 = perm64b, 8 = perm32
-static inline int permuted_row(int co, int cpl) {
-    if (cpl == 17) return (co & ~63) + perm64b_row_of_channel(co & 63);
-    return cpl == 16 ? (co & ~63) + perm64_row_of_channel(co & 63) : (co & ~31) + perm32_row_of_channel(co & 31);
-}
-
-// conv3x3_direct.hip
-int        direct_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);
-int        direct_variant_tiles(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);   // without the rolling-row kernel
-// conv3x3_c64.hip: rolling-row kernel for 64 -> 64 channel layers, weights in registers (variant 21)
-int        c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);
+// ---- kernel choice and launch (conv_kernel.h: the names, their properties, the packed weight layout) --------------------
+// The three ways a layer's kernel is chosen, each at the point where its weights are packed:
+ConvKernel direct_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);         // forward of the IR backbone (16-bit)
+ConvKernel direct_variant_tiles(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);   // other epilogues, backward passes
+ConvKernel linear_variant_x2(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);      // split precision
+// the one launch of a convolution by the kernel chosen for it (conv3x3_direct.hip)
+hipError_t launch_conv(ConvKernel k, int dtype, const ConvParams& p, hipStream_t st);
+hipError_t direct_set_attributes();
+// what they are made of, each file answering for its own kernel (ConvKernel::Igemm = does not apply)
+ConvKernel linear_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);   // conv3x3_linear.hip: 16-bit widths
+ConvKernel c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);      // conv3x3_c64.hip
+ConvKernel s2c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);    // conv3x3_s2c64.hip
+hipError_t launch_conv3x3_linear(ConvKernel k, int dtype, const ConvParams& p, hipStream_t st);
+hipError_t launch_conv3x3_c64(int dtype, const ConvParams& p, hipStream_t st);
+hipError_t launch_conv3x3_s2c64(int dtype, const ConvParams& p, hipStream_t st);
 hipError_t c64_set_attributes();
-hipError_t launch_conv3x3_c64(int variant, int dtype, const ConvParams& p, hipStream_t st);
-// conv3x3_s2c64.hip: the direct stride-2 kernel for 112 x 112 x 64 -> 56 x 56 x 64, projection shortcut as extra K-steps (variant 25)
-int        s2c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);
 hipError_t s2c64_set_attributes();
-hipError_t launch_conv3x3_s2c64(int variant, int dtype, const ConvParams& p, hipStream_t st);
+hipError_t linear_set_attributes();
+hipError_t linear_check_contract();   // probes the LDS out-of-range read contract; disables the linear kernel if it fails
 // front_c64.hip: stem + the first unit's conv1 in one rolling-row launch (the stem's activation stays in LDS; the quarter
 // of it the unit's projection shortcut samples goes to `xs`, [N][56][56][64])
 bool       front_c64_applies(int dtype, int H, int W, int C0, int Cout);
@@ -181,16 +167,6 @@ hipError_t launch_front_c64(int dtype, const ConvParams& conv1, const StemParams
 bool       unit_c64_applies(int dtype, const ConvParams& c1, const ConvParams& c2);
 hipError_t unit_c64_set_attributes();
 hipError_t launch_unit_c64(int dtype, const ConvParams& c1, const ConvParams& c2, hipStream_t st);
-int        direct_variant_cpl(int v);
-hipError_t direct_set_attributes();
-hipError_t launch_conv3x3_direct(int variant, int dtype, const ConvParams& p, hipStream_t st);
-// linear-tile variants (conv3x3_linear.hip), reached through the four functions above as variants 11..13
-int        linear_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);
-int        linear_variant_x2(int ksz, int stride, int pad, int H, int W, int Cin, int Cout);   // split precision: + the 112-wide layer
-int        linear_variant_cpl(int v);
-hipError_t linear_set_attributes();
-hipError_t linear_check_contract();   // probes the LDS out-of-range read contract; disables the linear kernel if it fails
-hipError_t launch_conv3x3_linear(int variant, int dtype, const ConvParams& p, hipStream_t st);
 // conv3x3_lat.hip: the latency form for launches of a handful of images (one wave per 32 x 32 output block, operands straight from L2)
 bool       conv3x3_lat_applies(int dtype, const ConvParams& p);
 hipError_t launch_conv3x3_lat(int dtype, const ConvParams& p, hipStream_t stream);

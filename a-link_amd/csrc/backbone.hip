@@ -95,7 +95,7 @@ struct BN { std::vector<double> a, b; };   // y = a*x + b
 struct ConvLayer {
     int Cin, Cout, ksz, stride, pad, Hin, Win, Hout, Wout;
     bool border_cls, has_alpha;
-    int variant = 0;                       // conv3x3_direct variant (0 = conv_igemm)
+    ConvKernel kernel = ConvKernel::Igemm; // the kernel its forward launch runs on (conv_kernel.h)
     int in_buf, out_buf, resid_buf;        // workspace buffer ids, -1 = none
     void*  d_w = nullptr;                   // T [Cout][K] permuted
     float* d_bias = nullptr;                // [ncls][Cout]
@@ -103,8 +103,8 @@ struct ConvLayer {
     std::string name;
     // input-gradient pass (alink_backbone_enable_grad): transposed + flipped folded weights for the
     // convolution that maps d(output) to d(input), and where this layer sits in its residual unit
-    void* d_wb = nullptr;                   // T [Cin][k*k*Cout], rows permuted for `bvariant`
-    int   bvariant = 0;                     // direct variant of the backward convolution (0 = conv_igemm)
+    void* d_wb = nullptr;                   // T [Cin][k*k*Cout], packed for `bkernel`
+    ConvKernel bkernel = ConvKernel::Igemm; // kernel of the backward convolution
     int   role = 0, unit = -1;              // 1 conv1, 2 shortcut, 3 conv2; index of the residual unit
     // ALINK_DT_F16X2: stored value = true value x 2^e.  e_w is fixed at finalize (folded weights), e_out by
     // alink_backbone_calibrate (the largest output the calibration images produce lands in [1024, 2048))
@@ -222,14 +222,14 @@ int upload(alink_backbone* bb, const std::vector<V>& h, void** d) {
 int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, const BN* pre,
                const BN& post, const std::vector<float>* prelu, const std::vector<float>* w_sc = nullptr,
                const BN* post_sc = nullptr) {
-    const int O = L.Cout, I = L.Cin, k = L.ksz, K = k * k * I, dt = bb->cfg.dtype;
-    const int I2 = w_sc ? L.Cin2 : 0, KR = K + I2;             // KR: weight row pitch of the 16-bit forms
+    const int O = L.Cout, I = L.Cin, k = L.ksz, dt = bb->cfg.dtype;
+    const int I2 = w_sc ? L.Cin2 : 0;
     const bool x2 = dt == ALINK_DT_F16X2;
     // split precision: the linear-tile kernel where it applies, the implicit-GEMM kernel everywhere else
-    L.variant = x2 ? linear_variant_x2(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout)
-                   : direct_variant(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout);
-    const int cpl = L.variant ? direct_variant_cpl(L.variant) : 16;
-    std::vector<uint16_t> wq(x2 ? (size_t)O * K * 2 : (size_t)O * KR);
+    L.kernel = x2 ? linear_variant_x2(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout)
+                  : direct_variant(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout);
+    const WeightLayout wl = weight_layout(L.kernel, k, I, x2, I2);
+    std::vector<uint16_t> wq(wl.size(O));
     std::vector<double> tapb((size_t)k * k * O, 0.0);          // [tap][co] shift contribution
     if (x2) {
         double mx = 0.0;
@@ -241,35 +241,23 @@ int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, co
     }
     const double wscale = std::ldexp(1.0, L.e_w);
     for (int co = 0; co < O; ++co) {
-        const int row = permuted_row(co, cpl);
         for (int ky = 0; ky < k; ++ky)
             for (int kx = 0; kx < k; ++kx) {
                 double tb = 0.0;
                 for (int ci = 0; ci < I; ++ci) {
                     const double wv = (double)w[(((size_t)co * I + ci) * k + ky) * k + kx];
                     const double ai = pre ? pre->a[ci] : 1.0;
-                    // K order: conv_igemm walks tap-major [tap][ci]; conv3x3_direct walks 64-channel
-                    // chunks outermost [ci/64][tap][ci%64]
-                    if (x2) {
-                        // rows of 2K: linear kernel [chunk][hi | lo][tap][64], implicit GEMM [tap][chunk][hi 64 | lo 64]
-                        const int tap = ky * k + kx, cc = ci >> 6;
-                        const size_t khi = L.variant ? (((size_t)cc * 2) * 9 + tap) * 64 + (ci & 63)
-                                                     : (((size_t)tap * (I >> 6) + cc) * 2) * 64 + (ci & 63);
-                        const size_t klo = khi + (L.variant ? 9 * 64 : 64);
-                        split16(post.a[co] * wv * ai * wscale, &wq[(size_t)row * 2 * K + khi], &wq[(size_t)row * 2 * K + klo]);
-                        if (pre) tb += wv * pre->b[ci];
-                        continue;
-                    }
-                    const size_t kidx = L.variant ? ((size_t)(ci >> 6) * 9 + (ky * 3 + kx)) * 64 + (ci & 63)
-                                                  : (size_t)(ky * k + kx) * I + ci;
-                    wq[(size_t)row * KR + kidx] = cvt(dt, (float)(post.a[co] * wv * ai));
+                    // the value: the weight scaled by the BN before (per input channel) and after (per output channel) it
+                    const size_t at = wl.at(co, ky * k + kx, ci);
+                    if (x2) split16(post.a[co] * wv * ai * wscale, &wq[at], &wq[at + wl.lo_offset()]);
+                    else    wq[at] = cvt(dt, (float)(post.a[co] * wv * ai));
                     if (pre) tb += wv * pre->b[ci];
                 }
                 tapb[(size_t)(ky * k + kx) * O + co] = post.a[co] * tb;
             }
         // fused shortcut: conv1sc (O, I2, 1, 1) scaled by its own BN, behind the taps of the same row
         for (int ci = 0; ci < I2; ++ci)
-            wq[(size_t)row * KR + K + ci] = cvt(dt, (float)(post_sc->a[co] * (double)(*w_sc)[(size_t)co * I2 + ci]));
+            wq[wl.at_shortcut(co, ci)] = cvt(dt, (float)(post_sc->a[co] * (double)(*w_sc)[(size_t)co * I2 + ci]));
     }
     const int ncls = L.border_cls ? 9 : 1;
     std::vector<float> bias((size_t)ncls * O);
@@ -300,22 +288,18 @@ int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, co
         // convolution always runs at stride 1 over the layer's INPUT grid (stride-2 layers see a
         // zero-inserted d(output)), with the layer's own padding.
         const int Hb = (L.ksz == 3) ? L.Hin : L.Hout, Wb = (L.ksz == 3) ? L.Win : L.Wout;
-        L.bvariant = direct_variant_tiles(L.ksz, 1, L.pad, Hb, Wb, O, I);
-        const int bcpl = L.bvariant ? direct_variant_cpl(L.bvariant) : 16;
-        const int KB = k * k * O;
-        std::vector<uint16_t> wb((size_t)I * KB);
-        for (int ci = 0; ci < I; ++ci) {
-            const size_t row = (size_t)permuted_row(ci, bcpl) * KB;
+        L.bkernel = direct_variant_tiles(L.ksz, 1, L.pad, Hb, Wb, O, I);
+        const WeightLayout bl = weight_layout(L.bkernel, k, O);
+        std::vector<uint16_t> wb(bl.size(I));
+        for (int ci = 0; ci < I; ++ci)
             for (int tap = 0; tap < k * k; ++tap) {
                 const int ft = k * k - 1 - tap, ky = ft / k, kx = ft % k;
                 for (int co = 0; co < O; ++co) {
                     const double wv = (double)w[(((size_t)co * I + ci) * k + ky) * k + kx];
                     const double ai = pre ? pre->a[ci] : 1.0;
-                    const size_t kidx = L.bvariant ? ((size_t)(co >> 6) * 9 + tap) * 64 + (co & 63) : (size_t)tap * O + co;
-                    wb[row + kidx] = cvt(dt, (float)(post.a[co] * wv * ai));
+                    wb[bl.at(ci, tap, co)] = cvt(dt, (float)(post.a[co] * wv * ai));
                 }
             }
-        }
         if ((rc = upload(bb, wb, &L.d_wb))) return rc;
     }
     return ALINK_OK;
@@ -753,13 +737,13 @@ static int plan_split(const alink_backbone* bb, const ConvLayer& L, int N) {
     if (!bb->split_small || N > SPLIT_MAX_N || L.Cin2) return 1;     // a fused shortcut is not split over K
     const long long M = (long long)N * L.Hout * L.Wout;
     const int ncc = L.Cin / 64;
+    const ConvKernelTraits t = traits(L.kernel);
     long long nwg;
     int units, kpu;                              // what a split divides: input chunks of 9 K-steps (linear) or K-steps (igemm)
-    if (L.variant >= 11 && L.variant <= 15) {
-        const int bn = (L.variant == 13 || L.variant == 15) ? 64 : 128;     // (the 64-channel form chosen for small batches doubles nwg: still <= 512)
-        nwg = ((M + 223) / 224) * (L.Cout / bn);
+    if (t.split == SplitUnit::Chunk) {
+        nwg = linear_grid(M, L.Cout, t.channel_block);     // (the 64-channel form chosen for small batches doubles nwg: still <= 512)
         units = ncc; kpu = 9;
-    } else if (L.variant == 0) {
+    } else if (t.split == SplitUnit::KStep) {
         const bool wide = (L.Cout % 128) == 0;
         nwg = wide ? ((M + 127) / 128) * (L.Cout / 128) : ((M + 255) / 256) * (L.Cout / 64);
         units = L.ksz * L.ksz * ncc; kpu = 1;
@@ -777,6 +761,17 @@ int g_sibling_aware = 1;
 extern "C" void alink_debug_set_sibling_aware(int on) { g_sibling_aware = on != 0; }
 int g_fine_max = 384;     // measured (r100, one launch at a time): the 64-channel form wins while the 128-channel grid fills < 3/4 of the 512 slots
 extern "C" void alink_debug_set_fine_max(int n) { g_fine_max = n; }
+// ConvParams::fine of a launch of M output pixels.  Few images (128-channel grid under 3/4 of the chip, g_fine_max): those
+// workgroups cover only part of the chip and each walks all of K alone on its CU; the 64-channel form doubles their number
+// and halves a K-step (bit-identical results: same weights, same summation order per output).
+// A shard of an in-call split runs beside its `siblings` - 1 others: it is their workgroups together that fill the chip —
+// measured for the 14- and 28-wide layers: IR-50, one 256-image batch +1.5 %, IR-100 at 292 images +1.7 %; the 7-wide
+// layers, 72 K-steps per workgroup, do better blind: −1 % otherwise at two 292-image shards.
+static int fine_form(ConvKernel k, long long M, int Cout, int siblings = 1) {
+    if (!traits(k).fine) return 0;
+    const int sib = (g_sibling_aware && k != ConvKernel::Linear7) ? siblings : 1;
+    return linear_grid(M, Cout, 128) * sib <= g_fine_max ? 1 : 0;
+}
 int g_ablate = 0;
 int g_stop_after = 0;       // diagnostic: alink_embed returns after this many convolution launches (0 = the whole chain)
 extern "C" void alink_debug_set_stop_after(int n) { g_stop_after = n; }
@@ -800,8 +795,8 @@ extern "C" void alink_debug_set_profile_reps(int n) { g_prof_reps = n < 1 ? 1 : 
 extern "C" void alink_debug_set_ablate(int a) { g_ablate = a; }
 extern "C" void alink_debug_set_stamps(void* p) { g_stamps = p; }
 
-// The conv2 that L (a plain unit's conv1) can share one unit_c64 launch with at batch N, or nullptr.  The linear-tile
-// variant 13 on both layers is what the fused launch reproduces (and it is only chosen where the LDS out-of-range probe
+// The conv2 that L (a plain unit's conv1) can share one unit_c64 launch with at batch N, or nullptr.  The 56-wide
+// linear-tile kernel on both layers is what the fused launch reproduces (and it is only chosen where the LDS out-of-range probe
 // passed, which the fused kernel's border handling rests on too).
 static const ConvLayer* fusable_unit(const alink_backbone* bb, const ConvLayer& L, int N, int S, bool cache) {
     if (!g_fuse_unit || (g_fuse_unit == 1 && N < FUSE_UNIT_MIN_N) || cache || S != 1 || g_ablate || g_stamps) return nullptr;
@@ -811,7 +806,7 @@ static const ConvLayer* fusable_unit(const alink_backbone* bb, const ConvLayer& 
     if (L.role != 1 || i + 1 >= bb->convs.size()) return nullptr;
     const ConvLayer& L2 = bb->convs[i + 1];
     if (L2.role != 3 || L2.unit != L.unit || L2.Cin2 || L2.in_buf != L.out_buf || L2.resid_buf != L.in_buf) return nullptr;
-    if (L.variant != 13 || L2.variant != 13 || L.stride != 1 || L2.stride != 1) return nullptr;
+    if (L.kernel != ConvKernel::Linear56 || L2.kernel != ConvKernel::Linear56 || L.stride != 1 || L2.stride != 1) return nullptr;
     if (L.Cin != 64 || L.Cout != 64 || L2.Cin != 64 || L2.Cout != 64 || L.Hin != 56 || L.Win != 56) return nullptr;
     if (plan_split(bb, L2, N) != 1) return nullptr;
     return &L2;
@@ -896,7 +891,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
     // quarter of it that the unit's projection shortcut samples lands in buffer 0 as a compact tensor.  16-bit inference
     // with the shortcut fused into conv2 only: the gradient pass, split precision and a stand-alone shortcut layer read
     // the whole stem activation.
-    const bool front = !x2 && !cache && bb->convs.size() >= 2 && bb->convs[0].variant == 21 && bb->convs[0].in_buf == 0 &&
+    const bool front = !x2 && !cache && bb->convs.size() >= 2 && bb->convs[0].kernel == ConvKernel::Roll112 && bb->convs[0].in_buf == 0 &&
                        bb->convs[1].Cin2 == 64 && bb->convs[1].in2_buf == 0 &&
                        front_c64_applies(cfg.dtype, cfg.height, cfg.width, 64, bb->convs[0].Cout) &&
                        plan_split(bb, bb->convs[0], N) == 1;
@@ -945,23 +940,13 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
         p.ablate = g_ablate;
         p.stagger = g_stagger;
         p.nprod = (x2 && !calib) ? bb->products : 0;
-        // few images (128-channel grid under 3/4 of the chip, g_fine_max): those workgroups cover only part of the chip and
-        // each walks all of K alone on its CU; the 64-channel form doubles their number and halves a K-step
-        // (bit-identical results: same weights, same summation order per output)
-        if (L.variant == 11 || L.variant == 12 || L.variant == 14) {
-            const long long nwg128 = (((long long)p.M + 223) / 224) * (L.Cout / 128);
-            // (a shard of an in-call split runs beside its siblings: it is their workgroups together that fill the chip —
-            // measured for the 14- and 28-wide layers: IR-50, one 256-image batch +1.5 %, IR-100 at 292 images +1.7 %; the
-            // 7-wide layers, 72 K-steps per workgroup, do better blind: −1 % otherwise at two 292-image shards)
-            const int sib = (g_sibling_aware && L.variant != 14) ? bb->siblings : 1;
-            p.fine = nwg128 * sib <= g_fine_max ? 1 : 0;
-        }
+        p.fine = fine_form(L.kernel, p.M, L.Cout, bb->siblings);
         int S = plan_split(bb, L, N);
         // the opt-in K split (order-changing) gives way where the bit-identical latency form applies: that one is faster
         if (S > 1) {
             ConvParams probe = p;
             probe.splitk = 1;
-            if (L.variant >= 11 ? conv3x3_lat_applies(cfg.dtype, probe) : (L.variant == 0 && conv_gemm_lat_applies(cfg.dtype, probe))) S = 1;
+            if (traits(L.kernel).split == SplitUnit::Chunk ? conv3x3_lat_applies(cfg.dtype, probe) : conv_gemm_lat_applies(cfg.dtype, probe)) S = 1;
         }
         if (x2) {
             p.ksteps_per_split *= 3;
@@ -974,8 +959,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
                     if (S > 1) {           // latency mode: K split into f32 slabs of raw accumulators, scales applied by the finish kernel
                         q.out = buf(6); q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S;
                     }
-                    if (L.variant) ALINK_HIP(launch_conv3x3_direct(L.variant, cfg.dtype, q, stream));
-                    else           ALINK_HIP(launch_conv_igemm(cfg.dtype, q, stream));
+                    ALINK_HIP(launch_conv(L.kernel, cfg.dtype, q, stream));
                     if (S > 1) ALINK_HIP(launch_conv_split_finish(cfg.dtype, p, (const float*)buf(6), S, stream));
                 }
                 return ALINK_OK;
@@ -1015,8 +999,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             if (S > 1) {
                 q.out = buf(6); q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S;
             }
-            if (L.variant) ALINK_HIP(launch_conv3x3_direct(L.variant, cfg.dtype, q, stream));
-            else           ALINK_HIP(launch_conv_igemm(cfg.dtype, q, stream));
+            ALINK_HIP(launch_conv(L.kernel, cfg.dtype, q, stream));
             if (S > 1) ALINK_HIP(launch_conv_split_finish(cfg.dtype, p, (const float*)buf(6), S, stream));
         }
         note(conv_flops(p), 1);
@@ -1293,8 +1276,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
             p.dact = base + GL.toff[u]; p.out = G(ids[1]); p.zero = bb->d_zero;
             p.N = N; p.H = H; p.W = W; p.Cin = c; p.Cout = c; p.Ho = H; p.Wo = W; p.stride = 1; p.ksz = 3; p.pad = 1;
             p.M = N * H * W; p.splitk = 1; p.ksteps_per_split = 9 * (c / 64);
-            if (B.bvariant) ALINK_HIP(launch_conv3x3_direct(B.bvariant, dt, p, st));
-            else            ALINK_HIP(launch_conv_igemm(dt, p, st));
+            ALINK_HIP(launch_conv(B.bkernel, dt, p, st));
         }
         const void* r = dy;                             // gradient arriving through the shortcut
         if (sc[u]) {
@@ -1312,8 +1294,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
             p.in = G(ids[1]); p.wgt = A.d_wb; p.bias = bb->d_zero_bias; p.resid = r; p.out = G(ids[3]); p.zero = bb->d_zero;
             p.N = N; p.H = H; p.W = W; p.Cin = c; p.Cout = cin; p.Ho = H; p.Wo = W; p.stride = 1; p.ksz = 3; p.pad = 1;
             p.M = N * H * W; p.splitk = 1; p.ksteps_per_split = 9 * (c / 64);
-            if (A.bvariant) ALINK_HIP(launch_conv3x3_direct(A.bvariant, dt, p, st));
-            else            ALINK_HIP(launch_conv_igemm(dt, p, st));
+            ALINK_HIP(launch_conv(A.bkernel, dt, p, st));
         }
         cur = ids[3];
     }
@@ -1343,15 +1324,11 @@ int alink_conv_nhwc(int dtype, const void* dev_in, const void* dev_w, const floa
     std::vector<uint16_t> h((size_t)Cout * K), hp((size_t)Cout * K);
     ALINK_HIP(hipStreamSynchronize(st));
     ALINK_HIP(hipMemcpy(h.data(), dev_w, h.size() * 2, hipMemcpyDeviceToHost));
-    const int variant = direct_variant(ksz, stride, pad, H, W, Cin, Cout);
-    const int cpl = variant ? direct_variant_cpl(variant) : 16;
-    for (int co = 0; co < Cout; ++co) {
-        const size_t r = (size_t)permuted_row(co, cpl) * K;
-        if (!variant) { memcpy(&hp[r], &h[(size_t)co * K], (size_t)K * 2); continue; }
-        for (int tap = 0; tap < 9; ++tap)
-            for (int ci = 0; ci < Cin; ++ci)
-                hp[r + ((size_t)(ci >> 6) * 9 + tap) * 64 + (ci & 63)] = h[(size_t)co * K + (size_t)tap * Cin + ci];
-    }
+    const ConvKernel kernel = direct_variant(ksz, stride, pad, H, W, Cin, Cout);
+    const WeightLayout wl = weight_layout(kernel, ksz, Cin);
+    for (int co = 0; co < Cout; ++co)
+        for (int tap = 0; tap < ksz * ksz; ++tap)
+            for (int ci = 0; ci < Cin; ++ci) hp[wl.at(co, tap, ci)] = h[(size_t)co * K + (size_t)tap * Cin + ci];
     void *d_wp = nullptr, *d_zero = nullptr;
     ALINK_HIP(hipMalloc(&d_wp, hp.size() * 2));
     ALINK_HIP(hipMalloc(&d_zero, 4096));
@@ -1365,11 +1342,8 @@ int alink_conv_nhwc(int dtype, const void* dev_in, const void* dev_w, const floa
     p.splitk = 1; p.ksteps_per_split = ksz * ksz * (Cin / 64);
     p.ablate = g_ablate; p.stamps = g_stamps;
     // fine: 1 / 0 force the 64- / 128-channel form of the linear-tile kernel, < 0 chooses as alink_embed does
-    if (variant == 11 || variant == 12 || variant == 14) {
-        const long long nwg128 = (((long long)p.M + 223) / 224) * (Cout / 128);
-        p.fine = fine < 0 ? (nwg128 <= g_fine_max ? 1 : 0) : (fine ? 1 : 0);
-    }
-    hipError_t e = variant ? launch_conv3x3_direct(variant, dtype, p, st) : launch_conv_igemm(dtype, p, st);
+    if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
+    hipError_t e = launch_conv(kernel, dtype, p, st);
     hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(d_wp);
     (void)hipFree(d_zero);
@@ -1396,8 +1370,8 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
     ALINK_HIP(hipStreamSynchronize(st));
     const int K = ksz * ksz * Cin, Ho = conv_out(H, ksz, stride, pad), Wo = conv_out(W, ksz, stride, pad);
     const size_t Min = (size_t)N * H * W, M = (size_t)N * Ho * Wo;
-    const int variant = linear_variant_x2(ksz, stride, pad, H, W, Cin, Cout);
-    const int cpl = variant ? direct_variant_cpl(variant) : 16;
+    const ConvKernel kernel = linear_variant_x2(ksz, stride, pad, H, W, Cin, Cout);
+    const WeightLayout wl = weight_layout(kernel, ksz, Cin, true);
     auto pack_act = [&](const float* dev, size_t rows, int C, int e, std::vector<uint16_t>& q) -> int {
         std::vector<float> h(rows * C);
         ALINK_HIP(hipMemcpy(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost));
@@ -1415,17 +1389,12 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
     {
         std::vector<float> h((size_t)Cout * K);
         ALINK_HIP(hipMemcpy(h.data(), dev_w, h.size() * 4, hipMemcpyDeviceToHost));
-        for (int co = 0; co < Cout; ++co) {
-            const size_t r = (size_t)permuted_row(co, cpl) * 2 * K;
+        for (int co = 0; co < Cout; ++co)
             for (int tap = 0; tap < ksz * ksz; ++tap)
                 for (int ci = 0; ci < Cin; ++ci) {
-                    const int cc = ci >> 6;
-                    const size_t khi = variant ? (((size_t)cc * 2) * 9 + tap) * 64 + (ci & 63)
-                                               : (((size_t)tap * (Cin >> 6) + cc) * 2) * 64 + (ci & 63);
-                    split16(std::ldexp((double)h[(size_t)co * K + (size_t)tap * Cin + ci], e_w), &qw[r + khi],
-                            &qw[r + khi + (variant ? 9 * 64 : 64)]);
+                    const size_t at = wl.at(co, tap, ci);
+                    split16(std::ldexp((double)h[(size_t)co * K + (size_t)tap * Cin + ci], e_w), &qw[at], &qw[at + wl.lo_offset()]);
                 }
-        }
     }
     void *d_in = nullptr, *d_res = nullptr, *d_w = nullptr, *d_out = nullptr, *d_zero = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_in); (void)hipFree(d_res); (void)hipFree(d_w); (void)hipFree(d_out); (void)hipFree(d_zero); };
@@ -1449,11 +1418,8 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
     p.acc_scale = std::ldexp(1.f, e_out - e_in - e_w);
     p.bias_scale = std::ldexp(1.f, e_out);
     p.res_scale = std::ldexp(1.f, e_out - e_res);
-    if (variant == 11 || variant == 12 || variant == 14) {
-        const long long nwg128 = (((long long)p.M + 223) / 224) * (Cout / 128);
-        p.fine = fine < 0 ? (nwg128 <= g_fine_max ? 1 : 0) : (fine ? 1 : 0);
-    }
-    X2_TRY(variant ? launch_conv3x3_direct(variant, ALINK_DT_F16X2, p, st) : launch_conv_igemm(ALINK_DT_F16X2, p, st));
+    if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
+    X2_TRY(launch_conv(kernel, ALINK_DT_F16X2, p, st));
     X2_TRY(hipStreamSynchronize(st));
     std::vector<uint16_t> qo(M * Cout * 2);
     X2_TRY(hipMemcpy(qo.data(), d_out, qo.size() * 2, hipMemcpyDeviceToHost));

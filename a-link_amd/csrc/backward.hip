@@ -11,14 +11,10 @@
 //   * stem_bwd_kernel       d(pixels) from d(stem output): PReLU' of the stored stem activation, the
 //                           transposed 3x3x3x64 convolution (K = 576 -> 3 outputs: VALU) and the 1/128
 //                           of the input normalisation
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
 
 // one wave per row
 template <typename T>

@@ -19,52 +19,10 @@
 //     from the zero page; a 16-pixel MFMA tile is 16 consecutive pixels of one row, lanes permuted by delta() and 16-B
 //     pieces XOR-swizzled by (position >> 1) & 7 as in the other kernels, so every ds_read_b128 is conflict-free;
 //   * epilogue as everywhere: folded-BN bias by border class, PReLU or residual, 8 consecutive channels per lane.
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + (bid >> 3);
-}
-
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
-
-// this wave's LDS-DMAs have landed and its own LDS reads have returned, then the workgroup barrier
-// (conv3x3_linear.hip, wait_dma_then_barrier: why both)
-__device__ __forceinline__ void wait_all_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// the same, leaving the wave's N youngest vector-memory operations in flight: at the top of a pass those are the output
-// stores of the pass before (issued after the prefetch DMAs this wait is for), whose latency nobody needs to see
-template <int N>
-__device__ __forceinline__ void wait_all_but_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 constexpr int NT = 256;
 
@@ -242,13 +200,13 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_c64_kernel(const ConvParams p) 
         const int y0 = (int)(band - (long long)n * bands_per_img) * BR;
         const long long img_row0 = (long long)n * H;
         // everyone is past the previous band's reads (and the table / border stores of the prologue): the ring is free
-        wait_all_then_barrier();
+        wait_then_barrier<0>();
         stage_rows(img_row0, y0 - 1, P + 2, 0);                     // rows y0-1 .. y0+P -> slots 0 .. P+1   (pass 0)
         stage_rows(img_row0, y0 + P + 1, P, P + 2);                 // rows of pass 1
         int s0 = 0;                                                  // slot of row (first output row of the pass) - 1
         f32x4 accA[2][TPWV], accB[2][TPWV];
         // ---- pass 0: its rows are everything but the wave's 7 youngest DMAs (those are pass 1's) -----------------------
-        wait_all_but_then_barrier<TPWV>();
+        wait_then_barrier<TPWV>();
         stage_rows(img_row0, y0 + 2 * P + 1, P, 2 * P + 2);         // rows of pass 2
         compute(accA, 0);
         s0 = P;
@@ -259,8 +217,10 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_c64_kernel(const ConvParams p) 
         // be computed among it.  (Pass 1: iteration 0 issued 7 DMAs only.)
 #pragma unroll 1
         for (int k = 1; k < BR / P; k += 2) {
-            if (k == 1) wait_all_but_then_barrier<TPWV>();
-            else        wait_all_but_then_barrier<VMI>();
+            // left in flight: what the iteration before issued — the prefetch DMAs and the output stores of the pass before,
+            // whose latency nobody needs to see
+            if (k == 1) wait_then_barrier<TPWV>();
+            else        wait_then_barrier<VMI>();
             if (k + 2 < BR / P) {
                 int sn = s0 + 2 * P + 2;
                 if (sn >= RING) sn -= RING;
@@ -271,7 +231,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_c64_kernel(const ConvParams p) 
             s0 += P;
             if (s0 >= RING) s0 -= RING;
             if (k + 1 < BR / P) {
-                wait_all_but_then_barrier<VMI>();
+                wait_then_barrier<VMI>();
                 if (k + 3 < BR / P) {
                     int sn = s0 + 2 * P + 2;
                     if (sn >= RING) sn -= RING;
@@ -297,10 +257,10 @@ bool g_use_c64 = true;
 
 extern "C" void alink_debug_set_c64(int on) { g_use_c64 = on != 0; }
 
-// 21: the rolling-row kernel for 112 x 112 x 64 -> 64 (0 = not applicable)
-int c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
-    if (!g_use_c64 || ksz != 3 || stride != 1 || pad != 1 || Cin != 64 || Cout != 64 || H != W) return 0;
-    return W == 112 ? 21 : 0;
+// the rolling-row kernel for 112 x 112 x 64 -> 64 (ConvKernel::Igemm = not applicable)
+ConvKernel c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+    if (!g_use_c64 || ksz != 3 || stride != 1 || pad != 1 || Cin != 64 || Cout != 64 || H != W) return ConvKernel::Igemm;
+    return W == 112 ? ConvKernel::Roll112 : ConvKernel::Igemm;
 }
 
 template <typename T, int EPI>
@@ -322,8 +282,8 @@ static void c64_launch(const ConvParams& p, unsigned grid, hipStream_t st) {
     else                                                         hipLaunchKernelGGL((conv3x3_c64_kernel<T, 112, 0>), dim3(grid), dim3(NT), lds, st, p);
 }
 
-hipError_t launch_conv3x3_c64(int variant, int dtype, const ConvParams& p, hipStream_t st) {
-    if (variant != 21 || p.ksz != 3 || p.stride != 1 || p.pad != 1 || p.Cin != 64 || p.Cout != 64 || p.H != 112 || p.W != 112)
+hipError_t launch_conv3x3_c64(int dtype, const ConvParams& p, hipStream_t st) {
+    if (p.ksz != 3 || p.stride != 1 || p.pad != 1 || p.Cin != 64 || p.Cout != 64 || p.H != 112 || p.W != 112)
         return hipErrorInvalidValue;
     if (p.splitk != 1 || p.dact || p.post_relu || p.in2 || p.N <= 0) return hipErrorInvalidValue;   // forward forms only
     if ((long long)p.N * p.H * p.W * 64 >= (1ll << 31)) return hipErrorInvalidValue;

@@ -21,40 +21,10 @@
 //     the 256 CUs exactly (the 128x128 im2col tiling gave 3.06 rounds).
 //   * Epilogue identical to conv_igemm: folded-BN bias with 9 border classes, PReLU, residual, store
 //     of 16 (TCW=4) or 8 (TCW=2) consecutive channels per lane.
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + (bid >> 3);
-}
-
-// column (0..15) inside a 16-pixel MFMA tile handled by MFMA column lr
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
 
 // Tile geometry of one instantiation.  A workgroup tile is R rows x TR column-blocks of 16.
 template <int WPX, int TPW, int TR>
@@ -69,17 +39,6 @@ struct Geo {
     __device__ static constexpr int row(int g, int u) { return modeA ? u / CPG : (modeB ? g : g * TPW + u); }
     __device__ static constexpr int cb(int g, int u)  { return modeA ? g * CPG + u % CPG : (modeB ? u : 0); }
 };
-
-template <int N>
-__device__ __forceinline__ void wait_dma_then_barrier() {
-    // counted wait: all but the N youngest LDS-DMA instructions of this wave have landed; then the
-    // workgroup barrier.  One asm statement with a memory clobber: no LDS access moves across it and
-    // hipcc adds no vmcnt(0) of its own (cdna_hip_programming.md §5 "Pipelining across barriers").
-    // lgkmcnt(0): the wave's own LDS reads have returned before it arrives — the compiler sinks the MFMAs that
-    // consume a step's last fragments (and their wait) below this statement, and a read still queued at the barrier
-    // can be overtaken by another wave's DMA into the buffer it is aimed at (conv3x3_linear.hip has the full story).
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 template <int A, int B>
 struct IC2 { static constexpr int a = A, b = B; };
@@ -210,7 +169,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_direct_kernel(const ConvP
 #pragma unroll
     for (int i = 0; i < XSLOTS; ++i) stage_x_slot(i, 0, 0);
     stage_w(0);
-    wait_dma_then_barrier<0>();
+    wait_then_barrier<0>();
     if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memtime();
 
     int wtog = 0;                       // byte offset of the weight buffer holding K-step t
@@ -243,7 +202,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_direct_kernel(const ConvP
 #pragma unroll
                     for (int u = 0; u < TPW; ++u) acc[tt][u] = mfma16<T>(wf[tt], pf[u], acc[tt][u]);
             }
-            wait_dma_then_barrier<0>();
+            wait_then_barrier<0>();      // end of the K-step: nothing stays in flight (the next step's weights have landed)
             wtog ^= WBYTES;
         };
         step(IC2<0, 0>{}); step(IC2<1, 0>{}); step(IC2<2, 0>{});
@@ -254,7 +213,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv3x3_direct_kernel(const ConvP
             // and wait — the co-resident workgroup keeps the matrix cores busy meanwhile
 #pragma unroll
             for (int i = 0; i < XSLOTS; ++i) stage_x_slot(i, 0, cc + 1);
-            wait_dma_then_barrier<0>();
+            wait_then_barrier<0>();
         }
     }
 
@@ -393,36 +352,41 @@ bool g_use_pair = true;     // prefer the two-workgroups-per-CU variants where t
 extern "C" void alink_debug_set_direct(int on) { g_use_direct = on != 0; }
 extern "C" void alink_debug_set_pair(int on) { g_use_pair = on != 0; }
 
-// Which direct variant (1..6) serves this convolution, 0 = none (use conv_igemm).
-// forward convolutions of the IR backbone: the rolling-row kernels (conv3x3_c64.hip, variant 21; its stride-2 form
-// conv3x3_s2c64.hip, variant 25) where they apply, else the tile kernels below (0 = none: conv_igemm).  Callers with other epilogues (backward pass: PReLU'; VGGFace2 / VGG16: post-ReLU) use
-// direct_variant_tiles.
-int direct_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+// Kernel choice, made once per layer where its weights are packed.  Three call patterns:
+//   * direct_variant: the 16-bit forward convolutions of the IR backbone — the rolling-row kernels (conv3x3_c64.hip and its
+//     stride-2 form conv3x3_s2c64.hip) where they apply, else as direct_variant_tiles;
+//   * direct_variant_tiles: everything whose epilogue the rolling-row kernels do not have (the backward passes: PReLU';
+//     VGGFace2 ResNet-50 / VGG16: ReLU after the residual) — the linear-tile kernel (conv3x3_linear.hip) where it applies,
+//     else the row-aligned tile kernels of this file;
+//   * linear_variant_x2 (conv3x3_linear.hip): split precision, which the tile kernels of this file and the rolling-row
+//     kernels have no form of — the linear-tile kernel at every width it has.
+// ConvKernel::Igemm = none of them applies: the implicit-GEMM kernel (conv_igemm.hip) takes the layer.
+ConvKernel direct_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
     if (g_use_direct) {
-        if (const int v = c64_variant(ksz, stride, pad, H, W, Cin, Cout)) return v;
-        if (const int v = s2c64_variant(ksz, stride, pad, H, W, Cin, Cout)) return v;
+        ConvKernel k = c64_variant(ksz, stride, pad, H, W, Cin, Cout);
+        if (k == ConvKernel::Igemm) k = s2c64_variant(ksz, stride, pad, H, W, Cin, Cout);
+        if (k != ConvKernel::Igemm) return k;
     }
     return direct_variant_tiles(ksz, stride, pad, H, W, Cin, Cout);
 }
-int direct_variant_tiles(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
-    if (!g_use_direct || ksz != 3 || stride != 1 || pad != 1 || Cin % 64 || Cout % 64) return 0;
-    if (const int lv = linear_variant(ksz, stride, pad, H, W, Cin, Cout)) return lv;     // 11..13: conv3x3_linear.hip
-    if (W > 14 * 8 || H < 1) return 0;
+ConvKernel direct_variant_tiles(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+    if (!g_use_direct || ksz != 3 || stride != 1 || pad != 1 || Cin % 64 || Cout % 64) return ConvKernel::Igemm;
+    const ConvKernel lk = linear_variant(ksz, stride, pad, H, W, Cin, Cout);
+    if (lk != ConvKernel::Igemm) return lk;
+    if (W > 14 * 8 || H < 1) return ConvKernel::Igemm;
     const int tr = (W + 15) / 16, pitch = (W + 2 + 15) / 16 * 16;
     if (g_use_pair) {
-        if (tr == 1 && pitch == 16 && W >= 12 && Cout % 128 == 0 && S1::lds_bytes(Cin) <= 80 * 1024) return 7;
-        if (tr == 2 && pitch == 32 && Cout % 128 == 0 && S3::lds_bytes(Cin) <= 80 * 1024) return 8;
+        if (tr == 1 && pitch == 16 && W >= 12 && Cout % 128 == 0 && S1::lds_bytes(Cin) <= 80 * 1024) return ConvKernel::PairW14C128;
+        if (tr == 2 && pitch == 32 && Cout % 128 == 0 && S3::lds_bytes(Cin) <= 80 * 1024) return ConvKernel::PairW28C128;
     }
-    if (tr == 1 && pitch == 16 && W >= 12 && Cout % 256 == 0 && D1::fits(Cin)) return 1;
-    if (tr == 2 && pitch == 32 && Cout % 256 == 0 && D2::fits(Cin)) return 2;
-    if (tr == 2 && pitch == 32 && Cout % 128 == 0 && D3::fits(Cin)) return 3;
-    if (tr == 4 && pitch == 64 && Cout % 128 == 0 && D4::fits(Cin)) return 4;
-    if (tr == 4 && pitch == 64 && D5::fits(Cin)) return 5;
-    if (tr == 7 && pitch == 128 && W == 112 && D6::fits(Cin)) return 6;
-    return 0;
+    if (tr == 1 && pitch == 16 && W >= 12 && Cout % 256 == 0 && D1::fits(Cin)) return ConvKernel::TileW14C256;
+    if (tr == 2 && pitch == 32 && Cout % 256 == 0 && D2::fits(Cin)) return ConvKernel::TileW28C256;
+    if (tr == 2 && pitch == 32 && Cout % 128 == 0 && D3::fits(Cin)) return ConvKernel::TileW28C128;
+    if (tr == 4 && pitch == 64 && Cout % 128 == 0 && D4::fits(Cin)) return ConvKernel::TileW56C128;
+    if (tr == 4 && pitch == 64 && D5::fits(Cin)) return ConvKernel::TileW56C64;
+    if (tr == 7 && pitch == 128 && W == 112 && D6::fits(Cin)) return ConvKernel::TileW112C64;
+    return ConvKernel::Igemm;
 }
-// weight-row permutation code of a variant (permuted_row): 17 -> perm64b (TCW = 4), 8 -> perm32 (TCW = 2)
-int direct_variant_cpl(int v) { return (v == 21 || v == 25) ? 8 : (v >= 11 ? linear_variant_cpl(v) : ((v == 1 || v == 2 || v == 7 || v == 8) ? 17 : 8)); }
 
 hipError_t direct_set_attributes() {
     hipError_t e;
@@ -438,23 +402,25 @@ hipError_t direct_set_attributes() {
     return linear_set_attributes();
 }
 
-hipError_t launch_conv3x3_direct(int variant, int dtype, const ConvParams& p, hipStream_t st) {
-    if (variant == 21) return launch_conv3x3_c64(variant, dtype, p, st);
-    if (variant == 25) return launch_conv3x3_s2c64(variant, dtype, p, st);
-    if (variant >= 11) return launch_conv3x3_linear(variant, dtype, p, st);
+hipError_t launch_conv(ConvKernel k, int dtype, const ConvParams& p, hipStream_t st) {
+    if (k == ConvKernel::Igemm) return launch_conv_igemm(dtype, p, st);
+    if (k == ConvKernel::Roll112) return launch_conv3x3_c64(dtype, p, st);
+    if (k == ConvKernel::Roll112S2) return launch_conv3x3_s2c64(dtype, p, st);
+    if (traits(k).channel_block) return launch_conv3x3_linear(k, dtype, p, st);
     if (dtype != ALINK_DT_BF16 && dtype != ALINK_DT_F16) return hipErrorInvalidValue;   // no split-precision form of these
     if (p.ksz != 3 || p.stride != 1 || p.pad != 1 || p.splitk != 1) return hipErrorInvalidValue;
     if ((long long)p.N * p.H * p.W * p.Cin >= (1ll << 31)) return hipErrorInvalidValue;
 #define L(V) (dtype == ALINK_DT_BF16 ? V::launch<__bf16>(p, st) : V::launch<_Float16>(p, st))
-    switch (variant) {
-        case 1: return L(D1);
-        case 2: return L(D2);
-        case 3: return L(D3);
-        case 4: return L(D4);
-        case 5: return L(D5);
-        case 6: return L(D6);
-        case 7: return L(S1);
-        case 8: return L(S3);
+    switch (k) {
+        case ConvKernel::TileW14C256: return L(D1);
+        case ConvKernel::TileW28C256: return L(D2);
+        case ConvKernel::TileW28C128: return L(D3);
+        case ConvKernel::TileW56C128: return L(D4);
+        case ConvKernel::TileW56C64:  return L(D5);
+        case ConvKernel::TileW112C64: return L(D6);
+        case ConvKernel::PairW14C128: return L(S1);
+        case ConvKernel::PairW28C128: return L(S3);
+        default: break;
     }
 #undef L
     return hipErrorInvalidValue;

@@ -24,51 +24,10 @@
 //
 // Weights, K-step order, epilogue and the two-workgroups-per-CU residency are those of the 4-wave
 // variants of conv3x3_direct.hip (same row permutation codes, so the packed weights are interchangeable).
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + (bid >> 3);
-}
-
-// pixel (0..15) inside a 16-pixel MFMA tile handled by MFMA column lr (see conv3x3_direct.hip)
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
-
-// End of a K-step (and of an input refill): this wave's LDS-DMAs have landed (vmcnt) AND its own LDS reads have returned
-// (lgkmcnt) before it arrives at the barrier.  The second wait is not optional: the MFMAs that consume a step's last
-// fragments carry no memory dependence, so the compiler sinks them — and the lgkmcnt wait they imply — BELOW this
-// statement; a wave then reaches the barrier with ds_reads still queued, a faster wave passes the barrier and issues the
-// DMA that re-fills the buffer those reads are aimed at, and the reads return the NEXT tile's bytes.  Seen as rare
-// wrong 224-pixel groups under multi-stream load (round 3: 1 row in 10^4 in the 128-channel forms, percent-level in the
-// register-rich 64-channel forms, where the compiler hoists eight reads across); single-stream runs never showed it.
-__device__ __forceinline__ void wait_dma_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 template <int A>
 struct IC { static constexpr int a = A; };
@@ -236,7 +195,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
     for (int i = tid; i < ncls * BN; i += NT) ebias[i] = p.bias[(i / BN) * p.Cout + n0 + (i % BN)] * (SP ? p.bias_scale : 1.f);
     if (p.alpha)
         for (int i = tid; i < BN; i += NT) ealpha[i] = p.alpha[n0 + i];
-    wait_dma_then_barrier();
+    wait_then_barrier<0>();
     if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memtime();
 
     int wtog = 0;
@@ -277,7 +236,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
 #pragma unroll
                     for (int u = 0; u < TPW; ++u) acc[tt][u] = mfma16<T>(wf[tt], pf[u], acc[tt][u]);
             }
-            wait_dma_then_barrier();
+            wait_then_barrier<0>();      // end of the K-step: nothing stays in flight (the next step's weights have landed)
             wtog ^= WBYTES;
         };
         step(IC<0>{}); step(IC<1>{}); step(IC<2>{});
@@ -291,7 +250,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
             const unsigned long long t0 = stamps ? __builtin_amdgcn_s_memtime() : 0ull;
             if (next_chunk) stage_x(cc_first + cc + 1, 0);
             else            stage_x(cc_first + cc, 1);
-            wait_dma_then_barrier();
+            wait_then_barrier<0>();
             if (stamps) refill_cycles += __builtin_amdgcn_s_memtime() - t0;
         }
       }
@@ -624,29 +583,29 @@ extern "C" int alink_debug_linear_contract_ok(void) {
     return dev >= 0 && dev < 64 && g_contract_ok[dev] ? 1 : 0;
 }
 
-// 11 / 12 / 13 / 14: linear-tile kernel for 14 / 28 / 56 / 7-wide square maps (0 = not applicable)
-int linear_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
-    if (ksz != 3 || stride != 1 || pad != 1 || H != W || Cin % 64) return 0;
+// the linear-tile kernel for 14 / 28 / 56 / 7-wide square maps (ConvKernel::Igemm = not applicable)
+ConvKernel linear_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+    if (ksz != 3 || stride != 1 || pad != 1 || H != W || Cin % 64) return ConvKernel::Igemm;
     const int dev = current_device();
-    if (dev < 0 || dev >= 64 || !g_contract_ok[dev]) return 0;        // the probe failed (or never ran) on this device
-    if ((g_linear_mode & 4) && W == 14 && Cout % 128 == 0) return 11;
-    if ((g_linear_mode & 2) && W == 28 && Cout % 128 == 0) return 12;
-    if ((g_linear_mode & 1) && W == 56 && Cout % 64 == 0) return 13;
-    if ((g_linear_mode & 8) && W == 7 && Cout % 128 == 0) return 14;
-    return 0;
+    if (dev < 0 || dev >= 64 || !g_contract_ok[dev]) return ConvKernel::Igemm;        // the probe failed (or never ran) on this device
+    if ((g_linear_mode & 4) && W == 14 && Cout % 128 == 0) return ConvKernel::Linear14;
+    if ((g_linear_mode & 2) && W == 28 && Cout % 128 == 0) return ConvKernel::Linear28;
+    if ((g_linear_mode & 1) && W == 56 && Cout % 64 == 0) return ConvKernel::Linear56;
+    if ((g_linear_mode & 8) && W == 7 && Cout % 128 == 0) return ConvKernel::Linear7;
+    return ConvKernel::Igemm;
 }
-// split precision: the same, plus the 112-wide layer (variant 15: 2 rows per workgroup, 64-channel tiles, 80 KB of LDS, two
+// split precision: the same, plus the 112-wide layer (Linear112: 2 rows per workgroup, 64-channel tiles, 80 KB of LDS, two
 // workgroups per CU) — the 16-bit modes take the row-aligned kernel there, split precision would otherwise fall to the
 // implicit GEMM, which stages the hi half of every input tile twice
-int linear_variant_x2(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
-    if (const int v = linear_variant(ksz, stride, pad, H, W, Cin, Cout)) return v;
-    if (ksz != 3 || stride != 1 || pad != 1 || H != W || Cin % 64) return 0;
+ConvKernel linear_variant_x2(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+    const ConvKernel k = linear_variant(ksz, stride, pad, H, W, Cin, Cout);
+    if (k != ConvKernel::Igemm) return k;
+    if (ksz != 3 || stride != 1 || pad != 1 || H != W || Cin % 64) return ConvKernel::Igemm;
     const int dev = current_device();
-    if (dev < 0 || dev >= 64 || !g_contract_ok[dev]) return 0;
-    if ((g_linear_mode & 16) && W == 112 && Cout % 64 == 0) return 15;
-    return 0;
+    if (dev < 0 || dev >= 64 || !g_contract_ok[dev]) return ConvKernel::Igemm;
+    if ((g_linear_mode & 16) && W == 112 && Cout % 64 == 0) return ConvKernel::Linear112;
+    return ConvKernel::Igemm;
 }
-int linear_variant_cpl(int v) { return (v == 13 || v == 15) ? 8 : 17; }
 
 hipError_t linear_set_attributes() {
     hipError_t e;
@@ -666,7 +625,7 @@ hipError_t linear_set_attributes() {
     return hipSuccess;
 }
 
-hipError_t launch_conv3x3_linear(int variant, int dtype, const ConvParams& p, hipStream_t st) {
+hipError_t launch_conv3x3_linear(ConvKernel k, int dtype, const ConvParams& p, hipStream_t st) {
     if (p.ksz != 3 || p.stride != 1 || p.pad != 1 || p.H != p.W) return hipErrorInvalidValue;
     // a handful of images: the latency form (same packed weights, same sums in the same order: bit-identical)
     if (conv3x3_lat_applies(dtype, p)) return launch_conv3x3_lat(dtype, p, st);
@@ -676,18 +635,20 @@ hipError_t launch_conv3x3_linear(int variant, int dtype, const ConvParams& p, hi
     // p.fine: the 64-channel form of the same kernel (weight rows are packed per 32-channel block, so both
     // forms read the same tensor, and every output is the same sum in the same order)
     if (p.fine) {
-        switch (variant) {
-            case 11: return p.W == 14 ? L(14, 2) : hipErrorInvalidValue;
-            case 12: return p.W == 28 ? L(28, 2) : hipErrorInvalidValue;
-            case 14: return p.W == 7 ? L(7, 2) : hipErrorInvalidValue;
+        switch (k) {
+            case ConvKernel::Linear14: return p.W == 14 ? L(14, 2) : hipErrorInvalidValue;
+            case ConvKernel::Linear28: return p.W == 28 ? L(28, 2) : hipErrorInvalidValue;
+            case ConvKernel::Linear7:  return p.W == 7 ? L(7, 2) : hipErrorInvalidValue;
+            default: break;
         }
     }
-    switch (variant) {
-        case 11: return p.W == 14 ? L(14, 4) : hipErrorInvalidValue;
-        case 12: return p.W == 28 ? L(28, 4) : hipErrorInvalidValue;
-        case 13: return p.W == 56 ? L(56, 2) : hipErrorInvalidValue;
-        case 14: return p.W == 7 ? L(7, 4) : hipErrorInvalidValue;
-        case 15: return p.W == 112 && dtype == ALINK_DT_F16X2 ? launch_one<_Float16, 112, 2, true>(p, st) : hipErrorInvalidValue;
+    switch (k) {
+        case ConvKernel::Linear14:  return p.W == 14 ? L(14, 4) : hipErrorInvalidValue;
+        case ConvKernel::Linear28:  return p.W == 28 ? L(28, 4) : hipErrorInvalidValue;
+        case ConvKernel::Linear56:  return p.W == 56 ? L(56, 2) : hipErrorInvalidValue;
+        case ConvKernel::Linear7:   return p.W == 7 ? L(7, 4) : hipErrorInvalidValue;
+        case ConvKernel::Linear112: return p.W == 112 && dtype == ALINK_DT_F16X2 ? launch_one<_Float16, 112, 2, true>(p, st) : hipErrorInvalidValue;
+        default: break;
     }
 #undef L
     return hipErrorInvalidValue;

@@ -19,40 +19,12 @@
 //   * one barrier per pass.
 // Reference: insightface fresnet stage1_unit1 conv2 (stride 2) + conv1sc / sc, inside model.forward at
 // /root/reference/code/face_model.py:90.
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
 
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int i32x4;
-
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
-
-template <int N>
-__device__ __forceinline__ void wait_all_but_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 constexpr int NT = 256;
 constexpr int WI = 112, HI = 112, WO = 56, HO = 56, C = 64;
@@ -204,14 +176,14 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_s2c64_kernel(const ConvParams p
     auto top_of_pass = [&](bool staged, bool loaded, bool stored) __attribute__((always_inline)) {
         const int n = (staged ? 7 : 0) + (loaded ? 4 : 0) + (stored ? 2 : 0);
         switch (n) {
-            case 13: wait_all_but_then_barrier<13>(); break;
-            case 11: wait_all_but_then_barrier<11>(); break;
-            case 9:  wait_all_but_then_barrier<9>(); break;
-            case 7:  wait_all_but_then_barrier<7>(); break;
-            case 6:  wait_all_but_then_barrier<6>(); break;
-            case 4:  wait_all_but_then_barrier<4>(); break;
-            case 2:  wait_all_but_then_barrier<2>(); break;
-            default: wait_all_but_then_barrier<0>(); break;
+            case 13: wait_then_barrier<13>(); break;
+            case 11: wait_then_barrier<11>(); break;
+            case 9:  wait_then_barrier<9>(); break;
+            case 7:  wait_then_barrier<7>(); break;
+            case 6:  wait_then_barrier<6>(); break;
+            case 4:  wait_then_barrier<4>(); break;
+            case 2:  wait_then_barrier<2>(); break;
+            default: wait_then_barrier<0>(); break;
         }
     };
 
@@ -225,7 +197,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_s2c64_kernel(const ConvParams p
         if (np > r1 - rr) np = (int)(r1 - rr);
         rr += np;
         const long long in_row0 = n * HI;
-        wait_all_but_then_barrier<0>();                              // everyone is past the reads of the run before
+        wait_then_barrier<0>();                              // everyone is past the reads of the run before
         stage_rows(in_row0, 2 * y0 - 1, 3);                          // pass 0's rows
         if (np > 1) stage_rows(in_row0, 2 * y0 + 2, 2);              // pass 1's
         vec8 xsA[2][2], xsB[2][2];
@@ -234,7 +206,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_s2c64_kernel(const ConvParams p
 #pragma unroll 1
         for (int k = 0; k < np; k += 2) {
             // pass k (shortcut operand in xsA), then pass k + 1 (xsB)
-            if (k == 0) { if (np > 1) wait_all_but_then_barrier<7 + (SC ? 4 : 0)>(); else wait_all_but_then_barrier<SC ? 4 : 0>(); }
+            if (k == 0) { if (np > 1) wait_then_barrier<7 + (SC ? 4 : 0)>(); else wait_then_barrier<SC ? 4 : 0>(); }
             else        top_of_pass(k + 1 < np, SC && k < np, true);
             if (k + 2 < np) stage_rows(in_row0, 2 * (y0 + k + 2), 2);
             if (SC && k + 1 < np) load_sc(n, y0 + k + 1, xsB);
@@ -257,10 +229,10 @@ bool g_use_s2c64 = true;
 
 extern "C" void alink_debug_set_s2direct(int on) { g_use_s2c64 = on != 0; }
 
-// 25: the direct stride-2 kernel for 112 x 112 x 64 -> 56 x 56 x 64 (0 = not applicable)
-int s2c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
-    if (!g_use_s2c64 || ksz != 3 || stride != 2 || pad != 1 || Cin != C || Cout != C || H != HI || W != WI) return 0;
-    return 25;
+// the direct stride-2 kernel for 112 x 112 x 64 -> 56 x 56 x 64 (ConvKernel::Igemm = not applicable)
+ConvKernel s2c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {
+    if (!g_use_s2c64 || ksz != 3 || stride != 2 || pad != 1 || Cin != C || Cout != C || H != HI || W != WI) return ConvKernel::Igemm;
+    return ConvKernel::Roll112S2;
 }
 
 hipError_t s2c64_set_attributes() {
@@ -271,8 +243,8 @@ hipError_t s2c64_set_attributes() {
     return hipSuccess;
 }
 
-hipError_t launch_conv3x3_s2c64(int variant, int dtype, const ConvParams& p, hipStream_t st) {
-    if (variant != 25 || p.ksz != 3 || p.stride != 2 || p.pad != 1 || p.Cin != C || p.Cout != C || p.H != HI || p.W != WI) return hipErrorInvalidValue;
+hipError_t launch_conv3x3_s2c64(int dtype, const ConvParams& p, hipStream_t st) {
+    if (p.ksz != 3 || p.stride != 2 || p.pad != 1 || p.Cin != C || p.Cout != C || p.H != HI || p.W != WI) return hipErrorInvalidValue;
     if (p.splitk != 1 || p.dact || p.post_relu || p.border_cls || p.N <= 0) return hipErrorInvalidValue;
     if (p.in2 && (p.Cin2 != C || p.alpha || p.resid)) return hipErrorInvalidValue;
     if ((long long)p.N * HI * WI * C >= (1ll << 31)) return hipErrorInvalidValue;

@@ -27,42 +27,11 @@
 //   * Epilogue fuses: folded-BN bias (9 position classes when a pre-activation BN shift was folded
 //     through zero padding), PReLU, residual add, conversion to T.  Split-K mode (the 25088->512
 //     FC) writes f32 partial slabs instead (reduced in fixed order by fc_finish: deterministic).
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// 16 bytes per lane, global -> LDS, no VGPR destination.  `lds_wave_base` must be wave-uniform:
-// lane l lands at lds_wave_base + 16*l.
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// Bijective XCD-aware remap (cdna_hip_programming.md §5 "XCD swizzle must be bijective"): blocks
-// with equal blockIdx % 8 share an XCD; give each such group one contiguous range of logical ids.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + (bid >> 3);
-}
 
 // SP (T = _Float16 only): the split-precision mode ALINK_DT_F16X2.  Every value is an f16 pair hi + lo (22 significant
 // bits); activations are [pixel][2 Cin] with each 64-channel chunk stored as [hi 64 | lo 64], weights

@@ -19,29 +19,12 @@
 // What is left of the launch's HBM traffic is the pixels (11 MB as u8) and conv1's output.
 // Reference: insightface fresnet conv0/bn0/relu0 + stage1_unit1 bn1/conv1/bn2/relu1, executed inside model.forward at
 // /root/reference/code/face_model.py:90.
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
 
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int i32x4;
-
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
 
 // every LDS operation of this wave has completed (the stem rows and pixel rows it wrote, the operand reads of the pass
 // before), then the workgroup barrier.  No vector-memory wait: nothing is DMA'd, loads land in registers (the compiler

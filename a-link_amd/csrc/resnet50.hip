@@ -20,7 +20,7 @@
 //
 // Input gradients (FGSM / PGD extension; 16-bit modes): alink_resnet50_enable_grad .. alink_resnet50_input_grad at the end of
 // this file walk the units backwards on the same convolution kernels; the kernels without a forward twin are in resnet50_bwd.hip.
-#include "alink_common.h"
+#include "conv_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,20 +32,6 @@
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 struct Stem7Params {
     const float* in;      // [N][H][W][3] f32
@@ -357,13 +343,13 @@ uint16_t cvt(int dtype, float f) { return dtype == ALINK_DT_BF16 ? f32_to_bf16_r
 struct Op {
     int kind;             // 0 stem7, 1 maxpool, 2 conv, 3 avgpool
     ConvParams cp;        // kind 2: everything but the per-call pointers/N/M
-    int variant = 0;
+    ConvKernel kernel = ConvKernel::Igemm;
     int in_buf = -1, out_buf = -1, resid_buf = -1;
     int e_w = 0, e_out = 0;   // split precision: stored value = true value x 2^e (weights: fixed at finalize; output: calibrated)
     std::string name;
     // input-gradient pass (alink_resnet50_enable_grad)
-    void* d_wb = nullptr;     // kind 2: T [Cin][k*k*Cout], the transposed (3x3: flipped) folded weights, rows permuted for `bvariant`
-    int bvariant = 0;         // direct variant of the backward convolution (0 = conv_igemm)
+    void* d_wb = nullptr;     // kind 2: T [Cin][k*k*Cout], the transposed (3x3: flipped) folded weights, packed for `bkernel`
+    ConvKernel bkernel = ConvKernel::Igemm;   // kernel of the backward convolution
     int unit = -1, role = 0;  // kind 2: index of the bottleneck unit; 1 1x1_reduce, 2 3x3, 3 1x1_increase, 4 1x1_proj
     int slot = -1;            // cached forward: which slot of the activation cache keeps this op's output (-1: scratch)
 };
@@ -456,32 +442,24 @@ int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int 
     op.kind = 2;
     op.name = name;
     const bool x2 = r->dtype == ALINK_DT_F16X2;
-    op.variant = x2 ? linear_variant_x2(k, stride, pad, Hin, Win, cin, cout) : direct_variant_tiles(k, stride, pad, Hin, Win, cin, cout);
-    const int cpl = op.variant ? direct_variant_cpl(op.variant) : 16;
+    op.kernel = x2 ? linear_variant_x2(k, stride, pad, Hin, Win, cin, cout) : direct_variant_tiles(k, stride, pad, Hin, Win, cin, cout);
+    const WeightLayout wl = weight_layout(op.kernel, k, cin, x2);
     const int K = k * k * cin;
-    std::vector<uint16_t> wq((size_t)cout * K * (x2 ? 2 : 1));
+    std::vector<uint16_t> wq(wl.size(cout));
     if (x2) {
         double mx = 0.0;
         for (int co = 0; co < cout; ++co)
             for (size_t i = 0; i < (size_t)K; ++i) mx = std::max(mx, std::fabs(a[co] * (double)w[i * cout + co]));
         op.e_w = scale_exp(mx);
     }
-    for (int co = 0; co < cout; ++co) {
-        const size_t row = (size_t)permuted_row(co, cpl) * K * (x2 ? 2 : 1);
+    for (int co = 0; co < cout; ++co)
         for (int tap = 0; tap < k * k; ++tap)
             for (int ci = 0; ci < cin; ++ci) {
                 const double v = a[co] * (double)w[((size_t)tap * cin + ci) * cout + co];
-                if (x2) {   // linear kernel [chunk][hi | lo][tap][64], implicit GEMM [tap][chunk][hi 64 | lo 64]
-                    const int cc = ci >> 6;
-                    const size_t khi = op.variant ? (((size_t)cc * 2) * 9 + tap) * 64 + (ci & 63)
-                                                  : (((size_t)tap * (cin >> 6) + cc) * 2) * 64 + (ci & 63);
-                    split16(std::ldexp(v, op.e_w), &wq[row + khi], &wq[row + khi + (op.variant ? 9 * 64 : 64)]);
-                    continue;
-                }
-                const size_t kidx = op.variant ? ((size_t)(ci >> 6) * 9 + tap) * 64 + (ci & 63) : (size_t)tap * cin + ci;
-                wq[row + kidx] = cvt(r->dtype, (float)v);
+                const size_t at = wl.at(co, tap, ci);
+                if (x2) split16(std::ldexp(v, op.e_w), &wq[at], &wq[at + wl.lo_offset()]);
+                else    wq[at] = cvt(r->dtype, (float)v);
             }
-    }
     std::vector<float> bias(cout);
     for (int co = 0; co < cout; ++co) bias[co] = (float)b[co];
     void* d_w = nullptr;
@@ -499,21 +477,15 @@ int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int 
     if (r->grad) {
         // d(input) = conv(d(output), Wb) at stride 1 on the OUTPUT grid: Wb[ci][tap'][co] = Wfolded[co][k*k-1-tap'][ci], the
         // values the forward multiplies by.  (A stride-2 1x1 reads only even positions: its result is scattered there.)
-        op.bvariant = direct_variant_tiles(k, 1, pad, Ho, Wo, cout, cin);
-        const int bcpl = op.bvariant ? direct_variant_cpl(op.bvariant) : 16;
-        const int KB = k * k * cout;
-        std::vector<uint16_t> wb((size_t)cin * KB);
-        for (int ci = 0; ci < cin; ++ci) {
-            const size_t row = (size_t)permuted_row(ci, bcpl) * KB;
+        op.bkernel = direct_variant_tiles(k, 1, pad, Ho, Wo, cout, cin);
+        const WeightLayout bl = weight_layout(op.bkernel, k, cout);
+        std::vector<uint16_t> wb(bl.size(cin));
+        for (int ci = 0; ci < cin; ++ci)
             for (int tap = 0; tap < k * k; ++tap) {
                 const int ft = k * k - 1 - tap;
-                for (int co = 0; co < cout; ++co) {
-                    const double v = a[co] * (double)w[((size_t)ft * cin + ci) * cout + co];
-                    const size_t kidx = op.bvariant ? ((size_t)(co >> 6) * 9 + tap) * 64 + (co & 63) : (size_t)tap * cout + co;
-                    wb[row + kidx] = cvt(r->dtype, (float)v);
-                }
+                for (int co = 0; co < cout; ++co)
+                    wb[bl.at(ci, tap, co)] = cvt(r->dtype, (float)(a[co] * (double)w[((size_t)ft * cin + ci) * cout + co]));
             }
-        }
         if ((rc = upload(r, wb, &op.d_wb))) return rc;
         if (role != 4) {                                   // the projection's output is not needed again
             op.slot = (int)r->slot_elems.size();
@@ -824,15 +796,13 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
                     p.acc_scale = std::ldexp(1.f, e - bexp[op.in_buf] - op.e_w);
                     p.bias_scale = std::ldexp(1.f, e);
                     p.res_scale = op.resid_buf >= 0 ? std::ldexp(1.f, e - bexp[op.resid_buf]) : 1.f;
-                    if (op.variant) ALINK_HIP(launch_conv3x3_direct(op.variant, r->dtype, p, st));
-                    else            ALINK_HIP(launch_conv_igemm(r->dtype, p, st));
+                    ALINK_HIP(launch_conv(op.kernel, r->dtype, p, st));
                     return ALINK_OK;
                 });
                 if (rc) return rc;
                 bexp[op.out_buf] = op.e_out;
             } else
-            if (op.variant) ALINK_HIP(launch_conv3x3_direct(op.variant, r->dtype, p, st));
-            else            ALINK_HIP(launch_conv_igemm(r->dtype, p, st));
+            ALINK_HIP(launch_conv(op.kernel, r->dtype, p, st));
             fl = conv_flops(p);
         } else {
             const int tot = n * 2048 / 8;
@@ -1036,8 +1006,7 @@ static int r50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_ima
         p.resid = resid; p.out = out; p.zero = r->d_zero;
         p.N = N; p.H = f.Ho; p.W = f.Wo; p.Cin = f.Cout; p.Cout = f.Cin; p.Ho = f.Ho; p.Wo = f.Wo; p.stride = 1; p.ksz = f.ksz;
         p.pad = f.pad; p.M = N * f.Ho * f.Wo; p.splitk = 1; p.ksteps_per_split = f.ksz * f.ksz * (f.Cout / 64);
-        if (op.bvariant) ALINK_HIP(launch_conv3x3_direct(op.bvariant, dt, p, st));
-        else             ALINK_HIP(launch_conv_igemm(dt, p, st));
+        ALINK_HIP(launch_conv(op.bkernel, dt, p, st));
         return ALINK_OK;
     };
     for (int u = n_units - 1; u >= 0; --u) {

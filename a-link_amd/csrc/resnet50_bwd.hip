@@ -13,14 +13,10 @@
 // scorer can be ~1e-6 and the average pool divides it by 49: below f16's normal range.  Every pass is linear in
 // dfeat, so the call multiplies dfeat by 2^e with max|dfeat| 2^e / 49 in [1, 2) — exact — and the stem kernel
 // multiplies the float32 result by 2^-e.  The scale lives in the caller's workspace (no host round trip).
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
 
 // one workgroup; scale[0] = 2^e, scale[1] = 2^-e.  A zero or non-finite maximum leaves e = 0.
 __global__ __launch_bounds__(1024) void r50_grad_scale_kernel(const float* __restrict__ dfeat, int count, float inv_hw,
@@ -168,14 +164,6 @@ __global__ void r50_maxpool_bwd_kernel(const T* __restrict__ y0, const T* __rest
 // tile (lane = pixel lr, channel group q: one 16-byte load straight from global memory — neighbouring taps and tiles re-read
 // the same lines from L1).  One wave owns one row of one class: its 112 pixels are 7 tiles, 7 accumulators; a weight
 // fragment is loaded once per tap and channel half and feeds the 7 MFMAs, whose 7 loads are in flight together.
-template <typename T> __device__ __forceinline__ f32x4 mfma16x16x32(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <> __device__ __forceinline__ f32x4 mfma16x16x32<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x4 mfma16x16x32<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
 constexpr int SB_TILES = 7;       // 16-pixel tiles per class row: rows of up to 224 pixels
 
 template <typename T>
@@ -219,7 +207,7 @@ __global__ __launch_bounds__(256) void r50_stem_bwd_kernel(const T* __restrict__
                     if (!ok) dv[t] = zero;
                 }
 #pragma unroll
-                for (int t = 0; t < SB_TILES; ++t) acc[t] = mfma16x16x32<T>(wv, dv[t], acc[t]);
+                for (int t = 0; t < SB_TILES; ++t) acc[t] = mfma16<T>(wv, dv[t], acc[t]);
             }
         }
     }

@@ -6,28 +6,13 @@
 //           0..255, HWC (code/readDFW.py:82) or CHW after FaceModel.get_input (code/face_model.py:83).
 //  finish : fixed-order reduction of the FC split-K slabs + folded bias, then the L2 row normalise
 //           that the reference does on the host with sklearn (code/face_model.py:92).
-#include "alink_common.h"
+#include "conv_device.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 
 constexpr int STEM_ROWS = 8;   // output rows per workgroup
 

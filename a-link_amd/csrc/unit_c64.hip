@@ -23,47 +23,10 @@
 // Bit-identical to the two conv3x3_linear launches: the same packed weight rows and delta() lane permutation, the same
 // (tap, K half) walk with the same 8-channel K slices on the same MFMA positions, conv1's epilogue (f32 accumulator + bias
 // by border class, PReLU as v > 0 ? v : v * a, rounding to T) and conv2's (accumulator + bias + (float)residual, rounding).
-#include "alink_common.h"
+#include "conv_device.h"
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(typename Vec8<T>::type a, typename Vec8<T>::type b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<__bf16>(bf16x8 a, bf16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<_Float16>(f16x8 a, f16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void dma16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)gsrc,
-        (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + (bid >> 3);
-}
-
-__device__ __forceinline__ int delta(int lr) { return lr < 4 ? 2 * lr : (lr < 12 ? 2 * (lr - 4) + 1 : 2 * (lr - 8)); }
-
-// the wave's N youngest vector-memory operations may stay in flight; its LDS reads / writes have returned; then the
-// workgroup barrier (N = 0 for the conv1 waves: what they have in flight are the DMAs of the rows the next pass reads;
-// N = this pass's stores for the conv2 waves, which nobody in the kernel reads)
-template <int N>
-__device__ __forceinline__ void wait_then_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 constexpr int W = 56;
 constexpr int NT = 512;
@@ -160,6 +123,8 @@ __device__ __forceinline__ void unit_wave(const UnitParams& p, char* smem, int c
     const int NP = npairs + 2;
 #pragma unroll 1
     for (int k = 0; k < NP; ++k) {
+        // conv1 waves wait for everything: what they have in flight are the DMAs of the rows this pass reads; the conv2
+        // waves leave the stores of the pass before in flight, which nobody in the kernel reads
         if (CONV == 1) wait_then_barrier<0>();
         else           wait_then_barrier<NTL>();
         // this pass: conv1 rows ya = R0 - 1 + 2k (+1), window slots (2k .. 2k + 3) of x; conv2 rows ya = R0 + 2k - 4 (+1),

@@ -12,7 +12,7 @@
 // its loader; every other convolution runs on conv3x3_direct / conv_igemm (bias as the folded-BN
 // bias slot, ReLU as a zero-slope PReLU epilogue).  New here: the 2x2 max-pool, whose last instance
 // writes the float32 features.
-#include "alink_common.h"
+#include "conv_device.h"
 
 #include <algorithm>
 #include <cstring>
@@ -22,10 +22,6 @@
 
 namespace alink {
 namespace {
-
-template <typename T> struct Vec8;
-template <> struct Vec8<__bf16>   { typedef bf16x8 type; };
-template <> struct Vec8<_Float16> { typedef f16x8 type; };
 
 // MaxPooling2D((2,2), strides 2) on NHWC T (floor on odd sizes); OUT = T, or float for the last pool
 template <typename T, typename OUT>
@@ -55,7 +51,8 @@ const int kWidth[5] = {64, 128, 256, 512, 512};
 struct VOp {
     int kind;          // 0 stem (conv1_1), 1 conv, 2 pool
     ConvParams cp;
-    int variant = 0, in_buf = 0, out_buf = 0, H = 0, W = 0, C = 0;
+    ConvKernel kernel = ConvKernel::Igemm;
+    int in_buf = 0, out_buf = 0, H = 0, W = 0, C = 0;
     std::string name;
 };
 
@@ -173,20 +170,15 @@ int alink_vgg16_finalize(alink_vgg16_t* r) {
     VOp st; st.kind = 0; st.out_buf = 0; st.H = H; st.W = W; st.name = "conv1_1"; r->ops.push_back(st);
     for (int b = 0; b < 5; ++b) {
         for (int l = (b == 0 ? 1 : 0); l < kBlocks[b]; ++l) {
-            const int cout = kWidth[b], K = 9 * cin;
+            const int cout = kWidth[b];
             const auto& w = r->raw.at(lname(b, l) + "/kernel");       // (3, 3, cin, cout)
             VOp op; op.kind = 1; op.name = lname(b, l);
-            op.variant = direct_variant_tiles(3, 1, 1, H, W, cin, cout);
-            const int cpl = op.variant ? direct_variant_cpl(op.variant) : 16;
-            std::vector<uint16_t> wq((size_t)cout * K);
-            for (int co = 0; co < cout; ++co) {
-                const size_t row = (size_t)permuted_row(co, cpl) * K;
+            op.kernel = direct_variant_tiles(3, 1, 1, H, W, cin, cout);
+            const WeightLayout wl = weight_layout(op.kernel, 3, cin);
+            std::vector<uint16_t> wq(wl.size(cout));
+            for (int co = 0; co < cout; ++co)
                 for (int tap = 0; tap < 9; ++tap)
-                    for (int ci = 0; ci < cin; ++ci) {
-                        const size_t kidx = op.variant ? ((size_t)(ci >> 6) * 9 + tap) * 64 + (ci & 63) : (size_t)tap * cin + ci;
-                        wq[row + kidx] = cvt16(r->dtype, w[((size_t)tap * cin + ci) * cout + co]);
-                    }
-            }
+                    for (int ci = 0; ci < cin; ++ci) wq[wl.at(co, tap, ci)] = cvt16(r->dtype, w[((size_t)tap * cin + ci) * cout + co]);
             void* d_w = nullptr;
             float* d_b = nullptr;
             if ((rc = upload(r, wq, &d_w))) return rc;
@@ -241,8 +233,7 @@ int alink_vgg16_embed(alink_vgg16_t* r, const float* dev_in, int n, int preproce
         } else if (op.kind == 1) {
             ConvParams p = op.cp;
             p.in = buf(op.in_buf); p.out = buf(op.out_buf); p.N = n; p.M = n * p.Ho * p.Wo;
-            if (op.variant) ALINK_HIP(launch_conv3x3_direct(op.variant, r->dtype, p, st));
-            else            ALINK_HIP(launch_conv_igemm(r->dtype, p, st));
+            ALINK_HIP(launch_conv(op.kernel, r->dtype, p, st));
         } else {
             const bool last = i + 1 == nops;
             const long long tot = (long long)n * (op.H / 2) * (op.W / 2) * (op.C / 8);

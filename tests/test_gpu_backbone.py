@@ -507,7 +507,7 @@ def test_split_precision_mode(gpu, capsys):
 @pytest.mark.parametrize("dtype,fine_max", [("f16x2", -1), ("bf16", 100000), ("f16", -1)])
 def test_concurrent_launches_are_bit_identical_to_serial(gpu, dtype, fine_max):
     """Regression for a write-after-read race between a K-step's last LDS reads and the next DMA into the same buffer
-    (csrc/conv3x3_linear.hip wait_dma_then_barrier: the wait for the wave's own reads was missing, and the compiler
+    (csrc/conv_device.h wait_then_barrier: the wait for the wave's own reads was missing, and the compiler
     sinks the consuming MFMAs below the barrier).  It only showed with launches overlapping on several streams: rare
     wrong 224-pixel groups, per-cent level in the register-rich 64-channel forms (forced everywhere here for bf16 via
     fine_max; split precision uses them at 7 wide by itself).  2,048 IR-50 images on 4 streams, four times, against the

@@ -6,6 +6,8 @@ Teacher: VGGFace2 ResNet-50 features at 224 x 224 scored by the ensemble; studen
 to end on lowRes x lowRes pixels.  Same flags and phases: train the low-res model and quit if it is not
 saved yet (code/ALINK_MTP.py:116-125), otherwise run the framework loop (alink_loop.run_alink_mtp),
 save, and report top-1 identification on the test split (:271-289).
+--noise also takes the gradient extensions `fgsm` / `pgd`: with feature_model=None they attack the student on the pixels the
+driver perturbs (noise.FGSM's pixel-model route: SmallRes.input_gradients, pulled back through the resize to lowRes).
 """
 import argparse
 import sys

@@ -127,6 +127,7 @@ PROTOTYPES = {
     "alink_smallres_apply_update": (_i, [_vp, _vp]),
     "alink_smallres_set_graph": (_i, [_vp, _i]),
     "alink_smallres_eval": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "alink_smallres_input_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "alink_smallres_mask_sizes": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     "alink_noise_gaussian": (_i, [_vp, _vp, _i64, _f, _f, _u64, _u64, _vp]),
     "alink_noise_speckle": (_i, [_vp, _vp, _i64, _f, _u64, _u64, _vp]),
@@ -140,6 +141,7 @@ PROTOTYPES = {
     "alink_perlin_vectors": (_i, [_i, _i, _u64, _u64, _vp, _vp]),
     "alink_noise_perlin": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), _vp, _vp]),
     "alink_resize_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "alink_resize_bilinear_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "alink_pgd_step": (_i, [_vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _vp]),
     "alink_perturb_images": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_perturb_images_multi": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -592,6 +592,57 @@ __global__ __launch_bounds__(256) void resize_kernel(const ResizeP p) {
     p.out[i] = r0 * (1.f - fy) + r1 * fy;
 }
 
+// The adjoint of resize_kernel under the same src_coord rule: din = Ry^T . dout . Rx per image and channel, in the gather form —
+// a thread owns a SOURCE element and sums, destination rows then columns ascending, the destination elements whose two-tap
+// footprints touch it.  No atomics: the sum's order is fixed, the result bit-reproducible, and a source element no tap touches
+// is an exact 0.0.  src_coord is monotone in d, so the touching destinations are a contiguous range: floor(f(d)) in {s - 1, s}
+// <=> d in [(s - 0.5) dst/src - 0.5, (s + 1.5) dst/src - 0.5).  The range below is that one widened by one on each side (the
+// rounding of f) and open at the clamped ends; src_coord itself then says what each candidate contributes.
+struct ResizeGradP {
+    const float* dout;     // [N][Ho][Wo][C]
+    float* din;            // [N][H][W][C]
+    int N, H, W, C, Ho, Wo;
+};
+
+__device__ __forceinline__ void touch_range(int s, int src, int dst, int& lo, int& hi) {
+    const double r = (double)dst / (double)src;
+    const int a = (int)floor(((double)s - 0.5) * r - 0.5) - 1, b = (int)ceil(((double)s + 1.5) * r - 0.5) + 1;
+    lo = (s == 0 || a < 0) ? 0 : a;
+    hi = (s == src - 1 || b > dst - 1) ? dst - 1 : b;
+}
+
+// what destination d takes from source s along one axis: (1 - w) if s is its first tap, plus w if s is its second
+__device__ __forceinline__ float tap_weight(int d, int s, int src, int dst) {
+    int s0, s1;
+    float w;
+    src_coord(d, src, dst, s0, s1, w);
+    return (s0 == s ? 1.f - w : 0.f) + (s1 == s ? w : 0.f);
+}
+
+__global__ __launch_bounds__(256) void resize_grad_kernel(const ResizeGradP p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)p.N * p.H * p.W * p.C) return;
+    const int c = (int)(i % p.C);
+    long long t = i / p.C;
+    const int x = (int)(t % p.W); t /= p.W;
+    const int y = (int)(t % p.H);
+    const int n = (int)(t / p.H);
+    int ylo, yhi, xlo, xhi;
+    touch_range(y, p.H, p.Ho, ylo, yhi);
+    touch_range(x, p.W, p.Wo, xlo, xhi);
+    const float* g = p.dout + (size_t)n * p.Ho * p.Wo * p.C + c;
+    float acc = 0.f;
+    for (int oy = ylo; oy <= yhi; ++oy) {
+        const float cy = tap_weight(oy, y, p.H, p.Ho);
+        if (cy == 0.f) continue;
+        for (int ox = xlo; ox <= xhi; ++ox) {
+            const float cx = tap_weight(ox, x, p.W, p.Wo);
+            if (cx != 0.f) acc = fmaf(cy * cx, g[((size_t)oy * p.Wo + ox) * p.C], acc);
+        }
+    }
+    p.din[i] = acc;
+}
+
 // ---- perturb_image (code/attack.py:5-29) -----------------------------------------------------------------
 // n candidates, each k x (x, y, r, g, b): copy the base image, then img[int(x), int(y)] = (r, g, b)
 // in list order (a later pixel overwrites an earlier one at the same position).  With split != 0
@@ -890,6 +941,19 @@ int alink_resize_bilinear(const float* dev_in, float* dev_out, int n, int H, int
     ALINK_REQUIRE(total < (1ll << 39), ALINK_EINVAL, "output too large");
     ResizeP p{dev_in, dev_out, n, H, W, C, Ho, Wo};
     hipLaunchKernelGGL(resize_kernel, g1(total), dim3(256), 0, (hipStream_t)stream, p);
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+int alink_resize_bilinear_grad(const float* dev_dout, float* dev_din, int n, int H, int W, int C, int Ho, int Wo,
+                               void* stream) {
+    ALINK_REQUIRE(dev_dout && dev_din && n >= 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, ALINK_EINVAL, "bad argument");
+    DeviceGuard dg(device_of_pointer(dev_din));
+    const long long total = (long long)n * H * W * C;
+    if (total == 0) return ALINK_OK;
+    ALINK_REQUIRE(total < (1ll << 39) && (long long)n * Ho * Wo * C < (1ll << 39), ALINK_EINVAL, "tensor too large");
+    ResizeGradP p{dev_dout, dev_din, n, H, W, C, Ho, Wo};
+    hipLaunchKernelGGL(resize_grad_kernel, g1(total), dim3(256), 0, (hipStream_t)stream, p);
     ALINK_HIP(hipGetLastError());
     return ALINK_OK;
 }

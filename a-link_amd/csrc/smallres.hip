@@ -196,6 +196,77 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const Conv1P p, const 
         if (kb + 8 * j < 28) o[(kb + 8 * j) * 32 + co] = acc[j];
 }
 
+// input gradient of the first layer (dz of 32 channels -> 3 pixel channels, 3x3 'same'): the transposed convolution
+//   dpix[n][y][x][c] = s * sum_{ky,kx,co} dz[n][y+1-ky][x+1-kx][co] * w[ky][kx][c][co]        (zero outside the image)
+// N = 3 is no GEMM's shape either.  A workgroup owns a 16 x 16 tile of one image's pixels and stages the tile's 18 x 18 halo
+// of dz in LDS (a pixel's nine 128-byte rows overlap its neighbours' ninefold; staged, a tile reads 1.27x its own dz), a thread
+// two pixels eight rows apart (one read of the weights serves both).  A pixel's sum runs tap-major (ky, kx), co ascending, one
+// fmaf chain per channel: it depends neither on the batch nor on the launch shape.  dz already carries relu'(a1).
+struct Conv1D {
+    const float *dz, *w;      // [nb][H][W][32]; (3,3,3,32) = [27][32]
+    float *dL, *dR;           // images 0 .. split-1 to dL, the rest to dR (dR == nullptr: all to dL); [n][H][W][3]
+    int nb, split, H, W;
+    float s;                  // 1/128 with prescale (the pixels entered as (x - 128)/128), else 1: a power of two, exact
+};
+constexpr int DG_TILE = 16, DG_HALO = DG_TILE + 2;
+constexpr int DG_PITCH = 36;  // floats per staged pixel: 16 lanes' 16-byte reads start 36 banks apart and cover all 64 once
+__global__ __launch_bounds__(128) void conv1_dgrad_kernel(const Conv1D p) {
+    __shared__ __attribute__((aligned(16))) float ws[27 * 32];
+    __shared__ __attribute__((aligned(16))) float hs[DG_HALO * DG_HALO * DG_PITCH];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 27 * 32; i += 128) ws[i] = p.w[i];
+    const int tiles_x = (p.W + DG_TILE - 1) / DG_TILE;
+    const int ty0 = ((int)blockIdx.x / tiles_x) * DG_TILE, tx0 = ((int)blockIdx.x % tiles_x) * DG_TILE, n = blockIdx.y;
+    const float* dz = p.dz + (size_t)n * p.H * p.W * 32;
+    // the halo in 16-byte pieces: clamped, always valid addresses, the value kept or dropped by a mask (conv1_patch's reason)
+    constexpr int PIECES = DG_HALO * DG_HALO * 8;
+#pragma unroll 7
+    for (int it = 0; it < (PIECES + 127) / 128; ++it) {
+        const int i = tid + it * 128;
+        const int hp = i >> 3, c4 = (i & 7) * 4;
+        const int iy = ty0 - 1 + hp / DG_HALO, ix = tx0 - 1 + hp % DG_HALO;
+        const bool ok = i < PIECES && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+        const int off = ok ? (iy * p.W + ix) * 32 + c4 : 0;
+        int mk = ok ? -1 : 0;
+        asm volatile("" : "+v"(mk));
+        const f32x4 v = *(const f32x4*)(dz + off);
+        f32x4 k;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k[j] = __int_as_float(__float_as_int(v[j]) & mk);
+        if (i < PIECES) *(f32x4*)(hs + hp * DG_PITCH + c4) = k;
+    }
+    __syncthreads();
+    const int lx = tid & 15, ly = tid >> 4;            // pixels (ly, lx) and (ly + 8, lx) of the tile
+    float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+#pragma unroll 1
+    for (int t = 0; t < 9; ++t) {             // (rolled: unrolled, the scheduler hoists every tap's LDS reads and spills)
+        const float* h0 = hs + ((ly + 2 - t / 3) * DG_HALO + lx + 2 - t % 3) * DG_PITCH;      // halo (0, 0) = image (ty0 - 1, tx0 - 1)
+        const float* h1 = h0 + 8 * DG_HALO * DG_PITCH;
+        const float* wt = ws + t * 96;
+#pragma unroll 4
+        for (int q = 0; q < 8; ++q) {
+            const f32x4 d0 = *(const f32x4*)(h0 + 4 * q), d1 = *(const f32x4*)(h1 + 4 * q);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 w = *(const f32x4*)(wt + c * 32 + 4 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { acc[0][c] = fmaf(d0[j], w[j], acc[0][c]); acc[1][c] = fmaf(d1[j], w[j], acc[1][c]); }
+            }
+        }
+    }
+    float* img = (p.dR && n >= p.split) ? p.dR + (size_t)(n - p.split) * p.H * p.W * 3 : p.dL + (size_t)n * p.H * p.W * 3;
+    const int x = tx0 + lx;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = ty0 + ly + 8 * r;
+        if (y < p.H && x < p.W) {
+            float* o = img + ((size_t)y * p.W + x) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c] = acc[r][c] * p.s;
+        }
+    }
+}
+
 }  // namespace
 
 struct alink_smallres {
@@ -238,6 +309,7 @@ struct alink_smallres {
     uint8_t* d_masks_own = nullptr;
     int stage_rows = 0;                // pairs the staging is sized for
     float* d_all_grads = nullptr;      // [tower grads | head grads] contiguous copy for all-reduce
+    float* ig_metrics = nullptr;       // {loss, accuracy} of alink_smallres_input_grad's head pass (nobody reads them)
     float* ws = nullptr;               // split-K slabs of sgemm
     size_t ws_floats = 0;
     std::vector<void*> allocs;
@@ -400,6 +472,7 @@ alink_smallres_t* alink_smallres_create(int img_h, int img_w, int feat, float lr
     // the tower's gradients are written where the data-parallel caller reads them: [tower | head] in one buffer
     rc |= sr_alloc(m, &m->d_all_grads, m->ntower + alink_head_num_params(m->head) + 4);      // + 4 spare floats (a data-parallel step's metrics travel with the gradients)
     m->d_g = m->d_all_grads;
+    rc |= sr_alloc(m, &m->ig_metrics, 4);
     m->ws_floats = (size_t)16 << 20;
     rc |= sr_alloc(m, &m->ws, m->ws_floats);
     rc |= sr_alloc(m, &m->ws2, m->ws_floats);
@@ -467,6 +540,47 @@ int alink_smallres_eval(alink_smallres_t* m, const float* dev_L, const float* de
     int rc = tower_fwd(m, dev_L, dev_R, n, prescale, nullptr, nullptr, (hipStream_t)stream);
     if (rc) return rc;
     return alink_head_eval(m->head, m->f, m->f + (size_t)n * m->feat, dev_y, n, dev_metrics, stream);
+}
+
+// The gradient of the loss with respect to the PIXELS: the inference forward (no Dropout; the pools still record their
+// argmaxes), the head's input gradients, then the dz chain of train_step_launches alone — no weight gradient, no side stream,
+// no update — and the first layer's transposed convolution on the vector units (conv1_dgrad_kernel).
+int alink_smallres_input_grad(alink_smallres_t* m, const float* dev_L, const float* dev_R, const float* dev_y,
+                              const float* dev_sw, int n, int prescale, float grad_scale, float* dev_dL, float* dev_dR,
+                              float* dev_probs, void* stream) {
+    ALINK_REQUIRE(m && dev_L && dev_R && dev_y && dev_dL && dev_dR, ALINK_EINVAL, "NULL argument");
+    ALINK_REQUIRE(n > 0 && n <= MAXN, ALINK_EINVAL, "n=%d outside 1..%d", n, MAXN);
+    DeviceGuard dg(m->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = tower_fwd(m, dev_L, dev_R, n, prescale, nullptr, nullptr, st);
+    if (rc) return rc;
+    const int nb = 2 * n;
+    float* fL = m->f;
+    float* fR = m->f + (size_t)n * m->feat;
+    // dz of the tower's Dense(feat, relu) from the head (its own gradients land in the head's buffer; nothing applies them)
+    if ((rc = alink_head_train_step_input_grads(m->head, fL, fR, dev_y, dev_sw, n, grad_scale, 1, m->gf, m->gf + (size_t)n * m->feat,
+                                                nullptr, m->ig_metrics, stream))) return rc;
+    {   // d(p2)[nb][flat] = dz . W^T
+        GemmP g{};
+        g.A = m->gf; g.B = m->d_p + m->oDW; g.C = m->gp2; g.M = nb; g.N = m->flat; g.K = m->feat;
+        g.lda = m->feat; g.ldb = m->feat; g.ldc = m->flat; g.amode = A_ROW; g.bmode = B_COLT;
+        if ((rc = run_gemm(m, g, 16, st))) return rc;
+    }
+    hipLaunchKernelGGL(pool_bwd_kernel, g1((long long)nb * m->H3 * m->W3 * 64), dim3(256), 0, st, m->gp2, m->arg2, (const uint8_t*)nullptr,
+                       1.f, m->a4, m->ga4, nb, m->H3, m->W3, 64);
+    if ((rc = dgrad(m, m->ga4, m->ga3, m->a3, 3, nb, m->P1h, m->P1w, st))) return rc;
+    if ((rc = dgrad(m, m->ga3, m->gp1, nullptr, 2, nb, m->P1h, m->P1w, st))) return rc;
+    hipLaunchKernelGGL(pool_bwd_kernel, g1((long long)nb * m->H1 * m->W1 * 32), dim3(256), 0, st, m->gp1, m->arg1, (const uint8_t*)nullptr,
+                       1.f, m->a2, m->ga2, nb, m->H1, m->W1, 32);
+    if ((rc = dgrad(m, m->ga2, m->ga1, m->a1, 1, nb, m->H, m->W, st))) return rc;
+    {
+        Conv1D c{m->ga1, m->d_p + m->oW[0], dev_dL, dev_dR, nb, n, m->H, m->W, prescale ? 0.0078125f : 1.f};
+        const int tiles = ((m->H + DG_TILE - 1) / DG_TILE) * ((m->W + DG_TILE - 1) / DG_TILE);
+        hipLaunchKernelGGL(conv1_dgrad_kernel, dim3(tiles, nb), dim3(128), 0, st, c);
+    }
+    ALINK_HIP(hipGetLastError());
+    if (dev_probs) return alink_head_forward(m->head, fL, fR, nullptr, nullptr, n, dev_probs, stream);
+    return ALINK_OK;
 }
 
 static bool g_smallres_overlap = true;

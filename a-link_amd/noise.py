@@ -230,6 +230,23 @@ def resize_images(images, new_size, device=None):
     return _ret(out, as_torch)
 
 
+def resize_images_grad(dout, src_size, device=None):
+    """The adjoint of resize_images: dout (n, Ho, Wo, C) is the gradient at the resized images, the result (n, H, W, C) the
+    gradient at the images of src_size = (width, height) they were resized from.  The identity when the sizes are equal."""
+    import torch
+    device = _abi.resolve_device(device)
+    g, as_torch = _as_device(dout, device)
+    n, Ho, Wo, Cc = g.shape
+    W, H = int(src_size[0]), int(src_size[1])
+    if (H, W) == (Ho, Wo):
+        return _ret(g.clone(), as_torch)
+    lib = _abi.init(device)
+    out = torch.empty((n, H, W, Cc), dtype=torch.float32, device=g.device)
+    _abi.check(lib.alink_resize_bilinear_grad(_abi.ptr(g), _abi.ptr(out), n, H, W, Cc, Ho, Wo, _abi.current_stream(device)),
+               "alink_resize_bilinear_grad")
+    return _ret(out, as_torch)
+
+
 class PredictionWrappedModel:
     """code/noise.py:153-168: X = stacked pair images (2H, W, 3); split, embed both halves, score."""
 
@@ -307,7 +324,11 @@ class FGSM(Noise):
         x' = clip(x -/+ eps * sign(d BCE(scorer(f(xl), f(xr)), target) / dx), 0, 255)
     targeted (default, like PixelAttacker.attack_all: target class = argmax(target_labels[i])) steps
     DOWN the loss of the target class; untargeted steps UP the loss of the given labels.
-    Needs a feature model that offers a gradient backbone — `ArcFace(..., grad_dtype=...)` / `RESNET50(..., grad_dtype=...)`
+    Two routes.  A PIXEL MODEL — `feature_model` None and a `model` that offers `input_gradients` and `shape`
+    (siamese.SmallRes, the Multi-PIE driver's student) — is attacked on the pixels it is given: per step both sides are resized
+    to the model's input size if they differ, ONE input_gradients(reduction="sum") call gives both sides' gradients at the same
+    iterate, resize_images_grad pulls them back, and the step, the eps-ball and the pixel clip apply at the SOURCE resolution.
+    Otherwise it needs a feature model that offers a gradient backbone — `ArcFace(..., grad_dtype=...)` / `RESNET50(..., grad_dtype=...)`
     (`feature_model.grad_backbone`), or `ArcFace(..., enable_grad=True)` (its own backbone) — and a DenseHead-backed pair
     model.  The attack runs wholly on that backbone: max_batch, embed_device, embed_with_cache, input_gradient."""
     steps, alpha, random_start = 1, None, False
@@ -328,6 +349,32 @@ class FGSM(Noise):
                             "or ArcFace(..., enable_grad=True)) and a DenseHead-backed pair model")
         return bb, head
 
+    def _pixel_model(self):
+        m = self.model
+        if self.feature_model is None and hasattr(m, "input_gradients") and hasattr(m, "shape"):
+            return m
+        return None
+
+    def _pixel_steps(self, pm, al, ar, xl, xr, y):
+        """the steps of the pixel-model route, in place on al / ar"""
+        lib = _abi.init(self.device)
+        Hm, Wm = int(pm.shape[0]), int(pm.shape[1])
+        src = (int(xl.shape[2]), int(xl.shape[1]))                 # (width, height), cv2's order
+        same = (Hm, Wm) == (int(xl.shape[1]), int(xl.shape[2]))
+        step = self.eps if self.alpha is None else float(self.alpha)
+        sign = -1.0 if self.targeted else 1.0
+        lo, hi = (self.clip if self.clip is not None else (float("-inf"), float("inf")))
+        for _ in range(self.steps):
+            rl = al if same else resize_images(al, (Wm, Hm), device=self.device)
+            rr = ar if same else resize_images(ar, (Wm, Hm), device=self.device)
+            gl, gr = pm.input_gradients([rl, rr], y, reduction="sum")
+            if not same:
+                gl, gr = resize_images_grad(gl, src, device=self.device), resize_images_grad(gr, src, device=self.device)
+            for adv, clean, grad in ((al, xl, gl), (ar, xr, gr)):
+                grad = grad.contiguous()
+                _abi.check(lib.alink_pgd_step(_abi.ptr(adv), _abi.ptr(clean), _abi.ptr(grad), adv.numel(), sign * step, self.eps,
+                                              float(lo), float(hi), self._stream()), "alink_pgd_step")
+
     def _targets(self, target_labels, n, out_dim):
         t = np.asarray(target_labels)
         cls = t.argmax(axis=1) if (t.ndim == 2 and t.shape[1] > 1) else t.reshape(n).astype(int)
@@ -344,11 +391,13 @@ class FGSM(Noise):
             if self.random_start:
                 self._next_seed(), self._next_seed()
             return [image_pairs[0], image_pairs[1]]
-        bb, head = self._parts()
+        pm = self._pixel_model()
+        if pm is None:
+            bb, head = self._parts()
         xl, as_torch = _as_device(image_pairs[0] if not isinstance(image_pairs[0], (list, tuple)) else np.stack(image_pairs[0]), self.device)
         xr, _ = _as_device(image_pairs[1] if not isinstance(image_pairs[1], (list, tuple)) else np.stack(image_pairs[1]), self.device)
         n = xl.shape[0]
-        y = torch.from_numpy(self._targets(target_labels, n, head.out_dim)).to(xl.device)
+        y = torch.from_numpy(self._targets(target_labels, n, 2 if pm is not None else head.out_dim)).to(xl.device)
         step = self.eps if self.alpha is None else float(self.alpha)
         sign = -1.0 if self.targeted else 1.0
         al, ar = xl.clone(), xr.clone()
@@ -359,6 +408,9 @@ class FGSM(Noise):
             for t in (al, ar):
                 _abi.check(lib.alink_noise_uniform(_abi.ptr(t), _abi.ptr(t), t.numel(), -self.eps, self.eps, self._next_seed(),
                                                    first * t[0].numel(), self._stream()), "alink_noise_uniform")
+        if pm is not None:
+            self._pixel_steps(pm, al, ar, xl, xr, y)
+            return [_ret(al, as_torch), _ret(ar, as_torch)]
         mb = bb.max_batch
         for _ in range(self.steps):
             for s in range(0, n, mb):

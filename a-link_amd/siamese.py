@@ -361,6 +361,12 @@ class SmallRes(SiameseNetwork, object):
     def predict(self, X):
         return self.siamese_net.predict(self.preprocess(X), batch_size=1024)
 
+    def input_gradients(self, X, Y, sample_weight=None, reduction="mean"):
+        """EXTENSION: (dL, dR), the gradient of the loss of the pairs X = [L, R] (RAW 0..255 pixels, what predict takes) against
+        the one-hot targets Y with respect to those raw pixels, as CUDA tensors — `preprocess` applied by the first kernel
+        (SmallResNet.input_gradients with prescale: no host pass over the pixels)."""
+        return self.siamese_net.input_gradients(X, Y, sample_weight=sample_weight, reduction=reduction, prescale=True)
+
 
 class FaceVGG16:
     """code/siamese.py:187-200: VGGFace VGG-16 pool5 features (25088-d at 224 x 224).  `weights`: path of

@@ -153,6 +153,42 @@ class SmallResNet(KerasFitMixin):
                        "alink_smallres_forward")
         return out if as_torch else out.cpu().numpy()
 
+    def input_gradients(self, x, y, sample_weight=None, reduction="mean", prescale=None):
+        """(dL, dR): the gradient of the Keras loss of the pairs x = [L, R] against the one-hot targets y — the inference forward,
+        no Dropout — with respect to the pixels of both sides, as CUDA float32 tensors of the inputs' shape (EXTENSION: what
+        noise.FGSM / PGD step along on a pixel student).  Host arrays or device tensors; any number of pairs, chunked by MAXN,
+        and the result is the gradient of the WHOLE call's loss whatever the chunking: reduction="mean" is the sample-weighted
+        batch mean over all rows (1 / count(sample_weight != 0)), "sum" the sum — each pair then gets the gradient of its own
+        loss, whatever batch it arrives in.  prescale (None: this model's own setting) = 1: the inputs are raw 0..255 pixels, the
+        first kernel applies (x - 128) / 128 and the gradient is with respect to the raw pixels.
+        Parameters and optimizer state are untouched; the handle's activation buffers and the head's gradient buffer are
+        overwritten, so not between dp_local_grads and dp_apply (include/alink_hip.h).
+        Known limit: sgemm's split plan depends on the batch size, so the BITS of a pair's gradient can depend on the batch it
+        arrives in (signs can differ where the gradient is within rounding of zero)."""
+        torch = self.torch
+        if reduction not in ("mean", "sum"):
+            raise ValueError("reduction must be 'mean' or 'sum', got %r" % (reduction,))
+        L, R, yd = self._dev(x[0]), self._dev(x[1]), self._dev(y)
+        n = L.shape[0]
+        if tuple(L.shape) != (n, self.H, self.W, 3) or tuple(R.shape) != tuple(L.shape) or tuple(yd.shape) != (n, 2):
+            raise ValueError("expected two (n, %d, %d, 3) image batches and (n, 2) targets, got %s, %s, %s"
+                             % (self.H, self.W, tuple(L.shape), tuple(R.shape), tuple(yd.shape)))
+        swd = None if sample_weight is None else self._dev(sample_weight).reshape(n)
+        if reduction == "sum":
+            scale = 1.0
+        else:
+            scale = 1.0 / max(1, n if swd is None else int((swd != 0).sum()))
+        pre = self.prescale if prescale is None else (1 if prescale else 0)
+        dL, dR = torch.empty_like(L), torch.empty_like(R)
+        st = _abi.current_stream(self.device)
+        for s in range(0, n, MAXN):
+            m = min(MAXN, n - s)
+            _abi.check(self.lib.alink_smallres_input_grad(self.h, _abi.ptr(L[s:s + m]), _abi.ptr(R[s:s + m]), _abi.ptr(yd[s:s + m]),
+                                                          _abi.ptr(None if swd is None else swd[s:s + m]), m, pre, scale,
+                                                          _abi.ptr(dL[s:s + m]), _abi.ptr(dR[s:s + m]), None, st),
+                       "alink_smallres_input_grad")
+        return dL, dR
+
     def draw_masks(self, n):
         """keep-masks (u8) for the 2n tower passes: Dropout(0.25) after each pool (code/siamese.py:146,153) — on the host, for callers
         that pass `masks=` explicitly (the parity tests hand the same masks to the oracle); train_on_batch draws its own on the device."""

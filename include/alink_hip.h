@@ -427,6 +427,18 @@ int alink_smallres_set_graph(alink_smallres_t* m, int on);
 int alink_smallres_apply_update(alink_smallres_t* m, void* stream);
 int alink_smallres_eval(alink_smallres_t* m, const float* dev_L, const float* dev_R, const float* dev_y, int n,
                         int prescale, float* dev_metrics, void* stream);
+/* EXTENSION (the FGSM / PGD noise of the Multi-PIE driver, which perturbs the pixels SmallRes reads): the gradient of the
+ * inference loss (no Dropout) with respect to the pixels of both sides, dev_dL / dev_dR (n, H, W, 3) f32; with `prescale` it is
+ * the gradient with respect to the raw 0..255 pixels (the first layer's factor 1/128 included).  dev_y (n, 2), dev_sw (n) or
+ * NULL, n <= 256; grad_scale as in alink_smallres_train_step (<= 0: the Keras batch mean 1 / count(sw != 0); > 0 replaces
+ * that factor — 1 gives every pair the gradient of its own loss).  dev_probs (optional): the (n, 2) outputs of the same forward.
+ * CONTRACT: parameters and Adadelta state are untouched; the handle's activation and activation-gradient buffers and the
+ * head's gradient buffer (alink_head_grads_dev) ARE overwritten — so never call it between a gradients-only step
+ * (alink_smallres_train_step with apply = 0) and its alink_smallres_apply_update; and it is as thread-unsafe as every other
+ * call on the handle.  No weight gradient is computed, nothing runs on the handle's side stream. */
+int alink_smallres_input_grad(alink_smallres_t* m, const float* dev_L, const float* dev_R, const float* dev_y,
+                              const float* dev_sw, int n, int prescale, float grad_scale, float* dev_dL, float* dev_dR,
+                              float* dev_probs, void* stream);
 /* sizes of the two dropout masks per tower image (elements): P1*P1*32 and P2*P2*64 */
 int alink_smallres_mask_sizes(const alink_smallres_t* m, int* per_image_1, int* per_image_2);
 
@@ -515,6 +527,12 @@ int alink_pgd_step(float* dev_adv, const float* dev_clean, const float* dev_grad
                    float lo, float hi, void* stream);
 int alink_resize_bilinear(const float* dev_in, float* dev_out, int n, int H, int W, int C, int Ho,
                           int Wo, void* stream);
+/* EXTENSION: the exact adjoint of alink_resize_bilinear — dev_din (n, H, W, C) = Ry^T . dev_dout (n, Ho, Wo, C) . Rx with the
+ * forward's own tap positions and weights — for gradients that must reach the pixels BEFORE a resize (noise.FGSM / PGD on a
+ * SmallRes student fed resized pairs).  Gather form, fixed summation order, no atomics: bit-reproducible, and exactly 0.0 on
+ * source elements no destination tap touches.  Runs on the device that owns the buffers; not in place. */
+int alink_resize_bilinear_grad(const float* dev_dout, float* dev_din, int n, int H, int W, int C, int Ho, int Wo,
+                               void* stream);
 /* attack.perturb_image (code/attack.py:5-29): n candidates x k pixels (x, y, r, g, b) as float64
  * (the DE population, truncated like astype(int)) written into n copies of dev_img (Hc, W, 3).
  * split = 0: dev_out is (n, Hc, W, 3); split = 1: dev_out is [2][n][Hc/2][W][3], the top and

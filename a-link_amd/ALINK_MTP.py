@@ -6,6 +6,10 @@ Teacher: VGGFace2 ResNet-50 features at 224 x 224 scored by the ensemble; studen
 to end on lowRes x lowRes pixels.  Same flags and phases: train the low-res model and quit if it is not
 saved yet (code/ALINK_MTP.py:116-125), otherwise run the framework loop (alink_loop.run_alink_mtp),
 save, and report top-1 identification on the test split (:271-289).
+--noise adversarial (the default, code/ALINK_MTP.py:53) is the reference's few-pixel differential-evolution attack on the student:
+the pairs are searched at the resolution the driver hands them and every candidate reaches the student at lowRes x lowRes through
+one fused perturb + split + resize launch (attack.py's pixel scorer; all the searches of a batch in lock-step).  Its settings —
+--attack_pixels 40, --attack_maxiter 50, --attack_popsize 250, the reference's (code/attack.py:91) — are options of this driver.
 --noise also takes the gradient extensions `fgsm` / `pgd`: with feature_model=None they attack the student on the pixels the
 driver perturbs (noise.FGSM's pixel-model route: SmallRes.input_gradients, pulled back through the resize to lowRes).
 """
@@ -31,7 +35,20 @@ def build_parser():
     p.add_argument("--resnet50_weights", default=None)
     p.add_argument("--pretrain_steps", type=int, default=32000)
     p.add_argument("--quiet", action="store_true")
+    # the few-pixel search of `--noise adversarial` (PixelAttacker.attack_all's defaults, code/attack.py:91)
+    p.add_argument("--attack_pixels", type=int, default=40)
+    p.add_argument("--attack_maxiter", type=int, default=50)
+    p.add_argument("--attack_popsize", type=int, default=250)
     return p
+
+
+def make_noise(name, model, FLAGS):
+    """the noise object of one --noise entry over the student; `adversarial` takes the search settings of the command line"""
+    cls = noise.get_relevant_noise(name)
+    if cls is noise.AdversarialNoise:
+        return cls(model=model, sess=None, feature_model=None, pixel_count=FLAGS.attack_pixels, maxiter=FLAGS.attack_maxiter,
+                   popsize=FLAGS.attack_popsize)
+    return cls(model=model, sess=None, feature_model=None)
 
 
 def main(argv=None):
@@ -50,8 +67,7 @@ def main(argv=None):
     ensemble = [siamese.SiameseNetwork(FEATURE_RES, FLAGS.ensemble_basepath + str(i), 1e-1)
                 for i in range(1, FLAGS.num_ensemble_models + 1)]
     lowResModel = siamese.SmallRes(low_res + (3,), FEATURE_RES, FLAGS.lowres_basemodel + str(FLAGS.lowRes), 1e-1)
-    ensembleNoise = [noise.get_relevant_noise(x)(model=lowResModel, sess=None, feature_model=None)
-                     for x in FLAGS.noise.split(',')]
+    ensembleNoise = [make_noise(x, lowResModel, FLAGS) for x in FLAGS.noise.split(',')]
     bag = committee.Bagging(ensemble, ensembleNoise)
     if not lowResModel.maybeLoadFromMemory():
         print('== Training lowres-faces model ==')

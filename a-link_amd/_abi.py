@@ -121,6 +121,7 @@ PROTOTYPES = {
     "alink_smallres_set_lr": (_i, [_vp, _f]),
     "alink_smallres_grads_dev": (_vp, [_vp]),
     "alink_smallres_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "alink_smallres_score_pairs": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "alink_smallres_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp]),
     "alink_smallres_train_step_drawn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp]),
     "alink_smallres_train_on_batch_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_uint64, _vp, _vp]),
@@ -145,6 +146,7 @@ PROTOTYPES = {
     "alink_pgd_step": (_i, [_vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _vp]),
     "alink_perturb_images": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_perturb_images_multi": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "alink_perturb_resize_multi": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_affine_warp": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_arcface_margin_workspace_bytes": (_sz, [_i, _i, _i]),
     "alink_arcface_margin_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -11,9 +11,14 @@ perturb kernel that writes both halves as two contiguous device batches (alink_p
 split = 1), two batched backbone launch chains and one fused pair-scoring kernel; only the
 population (popsize x 5k doubles) goes up and popsize energies come back.
 
-The fast path needs `model` to be a noise.PredictionWrappedModel over an ArcFace-style feature model
-(`.model.model.embed_device`) and a DenseHead-backed pair model; any other duck-typed model takes the
-reference's generic route (perturb on device, hand host arrays to model.predict).
+Two device routes, chosen by what `model` (a noise.PredictionWrappedModel) wraps:
+  * an ArcFace-style feature model (`.model.model.embed_device`) and a DenseHead-backed pair model: _FeatureScorer, the above;
+  * no feature model and a pair model that offers `shape` and a `siamese_net` with `score_pairs` (siamese.SmallRes, the
+    Multi-PIE driver's student): _PixelScorer — one launch writes both halves of every candidate at the MODEL's size
+    (alink_perturb_resize_multi: perturb + split + bilinear resize, bit-equal to the three separate steps, nothing at source
+    resolution in memory), SmallResNet.score_pairs scores them with bits that do not depend on the batch.  The pairs may have
+    any source size; the attacked images are returned at that size.
+Any other duck-typed model takes the reference's generic route (perturb on device, hand host arrays to model.predict).
 
 attack_all advances the searches of a pair batch in LOCK-STEP (_LockstepEngine): 400 x K images per launch instead of
 400, the success test read off the scores the generation already produced, the solvers' host bookkeeping hidden
@@ -85,31 +90,176 @@ def _device_parts(wrapped, search):
     return bb, head
 
 
+def _pixel_parts(wrapped):
+    """(net, (Hm, Wm), prescale) of the pixel-model objective — a PredictionWrappedModel without feature model whose pair model
+    offers `shape` and a `siamese_net` with `score_pairs` (siamese.SmallRes; the duck test of noise.FGSM._pixel_model) — or
+    TypeError.  The pair model must say what its `preprocess` is: the kernels' prescale (SmallRes) or the identity."""
+    pm = getattr(wrapped, "model", None)
+    net = getattr(pm, "siamese_net", None)
+    if not hasattr(wrapped, "feature_model") or wrapped.feature_model is not None or not hasattr(pm, "shape") \
+            or not hasattr(net, "score_pairs"):
+        raise TypeError("no device fast path for this model")
+    if getattr(pm, "_preprocess_is_prescale", False):
+        prescale = True
+    elif getattr(pm, "_identity_preprocess", False):
+        prescale = False
+    else:
+        raise TypeError("pair model preprocesses its inputs")
+    return net, (int(pm.shape[0]), int(pm.shape[1])), prescale
+
+
+# The objective of the search behind one small interface (_LockstepEngine, _DevicePairScorer):
+#   out_dim                          columns of a score row
+#   check_image(shape)               TypeError if a stacked pair image of this shape cannot be scored
+#   score_one(xs, img, device)       population of ONE pair -> (n, out_dim) device tensor        (lockstep = 0)
+#   lane_buffers(eng, lane, cap)     the device buffers a lane of `cap` candidates needs, as attributes of the lane
+#   enqueue(eng, lane, S, n, st)     perturb + score the lane's n candidates of S searches into lane.pred[:n]
+#   begin(eng) / end(eng), range_left(eng), recover(eng)      the optional range check of 16-bit storage
+class _FeatureScorer(object):
+    """stacked pair -> both halves at the backbone's size -> bb.embed_device -> head.predict_device"""
+
+    def __init__(self, wrapped, search):
+        self.bb, self.head = _device_parts(wrapped, search)
+        self.ub = getattr(self.bb, "bb", self.bb)            # the IRBackbone under a one-product screening view
+        self.out_dim = self.head.out_dim
+
+    def check_image(self, shape):
+        if len(shape) != 3 or shape[2] != 3 or shape[0] % 2 or (shape[0] // 2, shape[1]) != tuple(self.bb.image_size):
+            raise TypeError("stacked pair image %s does not match the backbone input" % (tuple(shape),))
+
+    def score_one(self, xs, img, device):
+        halves = _perturb_device(xs, img, True, device)
+        n = halves.shape[1]
+        emb = self.bb.embed_device(halves.reshape(2 * n, *halves.shape[2:]))
+        return self.head.predict_device(emb[:n], emb[n:])
+
+    def lane_buffers(self, eng, lane, cap):
+        import torch
+        lane.halves = torch.empty((2 * cap, eng.Hc // 2, eng.W, 3), dtype=torch.float32, device=eng.dev)
+        lane.emb = torch.empty((2 * cap, self.bb.emb), dtype=torch.float32, device=eng.dev)
+
+    def enqueue(self, eng, lane, S, n, st):
+        _abi.check(eng.lib.alink_perturb_images_multi(_abi.ptr(eng.imgs), _abi.ptr(lane.of_dev), eng.group, _abi.ptr(lane.xs_dev),
+                                                      n, eng.k, eng.Hc, eng.W, 1, _abi.ptr(lane.halves), st),
+                   "alink_perturb_images_multi")
+        self.bb.embed_device(lane.halves[:2 * n], out=lane.emb[:2 * n])
+        self.head.predict_device(lane.emb[:n], lane.emb[n:2 * n], out=lane.pred[:n])
+
+    def begin(self, eng):
+        ub = self.ub
+        self._saved_lazy = getattr(ub, "lazy_range_check", False)
+        if ub.dtype in ("f16", "f16x2"):
+            eng.torch.cuda.synchronize(eng.device)
+            ub.range_left()
+            ub.lazy_range_check = True
+
+    def end(self, eng):
+        self.ub.lazy_range_check = self._saved_lazy
+
+    def range_left(self, eng):
+        """16-bit storage only: did a forward of the lanes in flight leave the float16 range?  (The backbone checks this
+        itself after every call by synchronising the device — here the flag is read once per step, after the step's
+        own event, so that the other lane keeps the device busy.)  Split precision re-calibrates on the images in flight
+        (scales only go down), as IRBackbone._checked does, and the step is run again; plain f16 raises."""
+        ub = self.ub
+        if ub.dtype in ("f16", "f16x2") and ub.range_left(reset=False):
+            if ub.dtype != "f16x2":
+                eng.torch.cuda.synchronize(eng.device)
+                ub.range_left()
+                raise _abi.AlinkError("activations exceeded the float16 range in this network: build the backbone with dtype='bf16'")
+            self._recalibrate(eng)
+
+    def recover(self, eng):
+        """an enqueue raised: the other lane's forward raised the range flag while this one was being enqueued (the backbone
+        reads it at the start of a call when its check is deferred).  True: re-calibrated and run again."""
+        if self.ub.dtype != "f16x2":
+            return False
+        self._recalibrate(eng)
+        return True
+
+    def _recalibrate(self, eng):
+        ub = self.ub
+        eng.torch.cuda.synchronize(eng.device)
+        ub.range_left()
+        for lane in eng.lanes:
+            if lane.active:
+                ub.calibrate(lane.halves[:2 * len(lane.active) * eng.group], merge=True)
+        for lane in eng.lanes:
+            if lane.active:
+                eng._enqueue(lane)
+        eng.torch.cuda.synchronize(eng.device)
+        if ub.range_left():
+            raise _abi.AlinkError("activations exceeded the float16 range again after re-calibration")
+
+
+class _PixelScorer(object):
+    """stacked pair at ANY source size -> both halves at the pixel model's size in one launch (alink_perturb_resize_multi: no
+    source-resolution candidate exists) -> SmallResNet.score_pairs, whose rows do not depend on the batch.  float32 throughout:
+    no range check."""
+    begin = end = range_left = staticmethod(lambda eng: None)
+    recover = staticmethod(lambda eng: False)
+    out_dim = 2
+
+    def __init__(self, wrapped):
+        self.net, (self.Hm, self.Wm), self.prescale = _pixel_parts(wrapped)
+
+    def check_image(self, shape):
+        if len(shape) != 3 or shape[2] != 3 or shape[0] % 2:
+            raise TypeError("%s is not a stacked pair image" % (tuple(shape),))
+
+    def _perturb_resize(self, lib, imgs, of_dev, group, xs_dev, n, k, Hc, W, out, st):
+        _abi.check(lib.alink_perturb_resize_multi(_abi.ptr(imgs), _abi.ptr(of_dev), group, _abi.ptr(xs_dev), n, k, Hc, W, self.Hm, self.Wm,
+                                                  _abi.ptr(out), st), "alink_perturb_resize_multi")
+
+    def score_one(self, xs, img, device):
+        import torch
+        xs = np.ascontiguousarray(np.asarray(xs, dtype=np.float64))
+        n, m = xs.shape
+        if m % 5:
+            raise ValueError("array split does not result in an equal division")       # np.split (code/attack.py:22)
+        halves = torch.empty((2, n, self.Hm, self.Wm, 3), dtype=torch.float32, device=img.device)
+        self._perturb_resize(_abi.init(device), img, None, 1, torch.from_numpy(xs).to(img.device), n, m // 5, img.shape[0], img.shape[1],
+                             halves, _abi.current_stream(device))
+        return self.net.score_pairs(halves[0], halves[1], prescale=self.prescale)
+
+    def lane_buffers(self, eng, lane, cap):
+        import torch
+        lane.halves = torch.empty((2 * cap, self.Hm, self.Wm, 3), dtype=torch.float32, device=eng.dev)
+
+    def enqueue(self, eng, lane, S, n, st):
+        self._perturb_resize(eng.lib, eng.imgs, lane.of_dev, eng.group, lane.xs_dev, n, eng.k, eng.Hc, eng.W, lane.halves, st)
+        self.net.score_pairs(lane.halves[:n], lane.halves[n:2 * n], out=lane.pred[:n], prescale=self.prescale)
+
+
+def _scorer_for(wrapped, search):
+    """the feature-model scorer, else the pixel scorer, else TypeError (the caller takes the generic route)"""
+    try:
+        return _FeatureScorer(wrapped, search)
+    except TypeError:
+        return _PixelScorer(wrapped)
+
+
 class _DevicePairScorer(object):
     """The fused objective: population -> P(class) of the perturbed pair, all on device.
     search="screen": the candidates of the search are embedded by the feature model's 16-bit SCREENING form where it has one
     (ArcFace.screen: 44 k embeddings/s against the exact mode's 15 k — the search is 20,400 backbone forwards per pair, 1.4 s in
     the exact mode).  The reference's search is a random one (differential evolution, unseeded: code/attack.py:81-83), so which
     arithmetic ranks its candidates is not contractual; the image it RETURNS is embedded like any other by whoever calls the
-    attack.  search="bf16": a bfloat16 handle on the same checkpoint (ArcFace.search_handle), the fastest form.  Default "exact"."""
+    attack.  search="bf16": a bfloat16 handle on the same checkpoint (ArcFace.search_handle), the fastest form.  Default "exact".
+    A pixel model (_PixelScorer) has one arithmetic only: `search` does not apply to it."""
 
     def __init__(self, wrapped, image, device=None, search="exact"):
         import torch
-        self.bb, self.head = _device_parts(wrapped, search)
-        bb = self.bb
+        self.scorer = _scorer_for(wrapped, search)
+        self.bb, self.head = getattr(self.scorer, "bb", None), getattr(self.scorer, "head", None)
         image = np.asarray(image, dtype=np.float32)
-        Hc, W, _ = image.shape
-        if Hc % 2 or (Hc // 2, W) != tuple(bb.image_size):
-            raise TypeError("stacked pair image %s does not match the backbone input" % (image.shape,))
+        self.scorer.check_image(image.shape)
         device = _abi.resolve_device(device)
         self.img = torch.from_numpy(np.ascontiguousarray(image)).to("cuda:%d" % device)
         self.device = device
 
     def predict(self, xs):
-        halves = _perturb_device(xs, self.img, True, self.device)
-        n = halves.shape[1]
-        emb = self.bb.embed_device(halves.reshape(2 * n, *halves.shape[2:]))
-        return self.head.predict_device(emb[:n], emb[n:]).cpu().numpy()
+        return self.scorer.score_one(xs, self.img, self.device).cpu().numpy()
 
 
 class _Lane(object):
@@ -125,10 +275,9 @@ class _Lane(object):
         self.of_host = torch.empty(slots, dtype=torch.int32).pin_memory()
         self.of_np = self.of_host.numpy()
         self.of_dev = torch.empty(slots, dtype=torch.int32, device=dev)
-        self.halves = torch.empty((2 * cap, eng.Hc // 2, eng.W, 3), dtype=torch.float32, device=dev)
-        self.emb = torch.empty((2 * cap, eng.bb.emb), dtype=torch.float32, device=dev)
-        self.pred = torch.empty((cap, eng.head.out_dim), dtype=torch.float32, device=dev)
-        self.pred_host = torch.empty((cap, eng.head.out_dim), dtype=torch.float32).pin_memory()
+        eng.scorer.lane_buffers(eng, self, cap)              # halves (and what lies between them and the scores)
+        self.pred = torch.empty((cap, eng.scorer.out_dim), dtype=torch.float32, device=dev)
+        self.pred_host = torch.empty((cap, eng.scorer.out_dim), dtype=torch.float32).pin_memory()
         self.pred_np = self.pred_host.numpy()
         self.done = torch.cuda.Event()
         self.active = []                         # the searches whose candidates are in flight, in row order
@@ -153,40 +302,36 @@ class _LockstepEngine(object):
         so the row equals what the reference's extra predict() would return;
       * a search that stops (success, or maxiter) frees its place in the lane for the next pair.
     Every search sees exactly the energies it would see alone, so the attacked images do not depend on K
-    (tests/test_gpu_noise.py::test_lockstep_attack_equals_the_sequential_attack)."""
+    (tests/test_gpu_noise.py::test_lockstep_attack_equals_the_sequential_attack).
+    What scores a lane is a SCORER (_FeatureScorer: halves -> backbone -> DenseHead; _PixelScorer: halves at the pixel model's
+    size -> SmallResNet.score_pairs, tests/test_gpu_smallres_attack.py): the engine itself knows neither."""
 
     def __init__(self, wrapped, images, search, device=None):
         import torch
         self.torch = torch
-        self.bb, self.head = _device_parts(wrapped, search)
+        self.scorer = _scorer_for(wrapped, search)
         self.device = _abi.resolve_device(device)
         self.dev = "cuda:%d" % self.device
         self.lib = _abi.init(self.device)
         first = images[0]
+        self.scorer.check_image(tuple(first.shape))
         self.Hc, self.W = int(first.shape[0]), int(first.shape[1])
-        if len(first.shape) != 3 or first.shape[2] != 3 or self.Hc % 2 or (self.Hc // 2, self.W) != tuple(self.bb.image_size):
-            raise TypeError("stacked pair image %s does not match the backbone input" % (tuple(first.shape),))
         # the stacked pair images of the whole call stay resident (301 KB each at 112 x 112: 3,840 pairs = 1.2 GB of 288)
         if isinstance(images, torch.Tensor):                     # (n, 2H, W, 3) already on a device: no trip through the host
             self.imgs = images.to(self.dev, torch.float32).contiguous()
         else:
             host = np.ascontiguousarray(np.stack([np.asarray(im, dtype=np.float32) for im in images]))
             self.imgs = torch.from_numpy(host).to(self.dev)
-        self.ub = getattr(self.bb, "bb", self.bb)            # the IRBackbone under a one-product screening view
 
     # -- one launch ----------------------------------------------------------------------------------------------------
     def _enqueue(self, lane):
-        """the device side of a step: candidates up, perturb, embed both halves, score, scores down (all asynchronous)"""
+        """the device side of a step: candidates up, perturb and score (the scorer), scores down (all asynchronous)"""
         S = len(lane.active)
         n = S * self.group
         st = _abi.current_stream(self.device)
         lane.xs_dev[:n].copy_(lane.xs_host[:n], non_blocking=True)
         lane.of_dev[:S].copy_(lane.of_host[:S], non_blocking=True)
-        _abi.check(self.lib.alink_perturb_images_multi(_abi.ptr(self.imgs), _abi.ptr(lane.of_dev), self.group, _abi.ptr(lane.xs_dev),
-                                                       n, self.k, self.Hc, self.W, 1, _abi.ptr(lane.halves), st),
-                   "alink_perturb_images_multi")
-        self.bb.embed_device(lane.halves[:2 * n], out=lane.emb[:2 * n])
-        self.head.predict_device(lane.emb[:n], lane.emb[n:2 * n], out=lane.pred[:n])
+        self.scorer.enqueue(self, lane, S, n, st)
         lane.pred_host[:n].copy_(lane.pred[:n], non_blocking=True)
         lane.done.record(self.torch.cuda.current_stream(self.device))
 
@@ -200,38 +345,8 @@ class _LockstepEngine(object):
         try:
             self._enqueue(lane)
         except _abi.AlinkError:
-            # the other lane's forward raised the range flag while this one was being enqueued (the backbone reads it at
-            # the start of a call when its check is deferred)
-            if self.ub.dtype != "f16x2":
+            if not self.scorer.recover(self):
                 raise
-            self._recalibrate()
-
-    def _range_left(self):
-        """16-bit storage only: did a forward of the lanes in flight leave the float16 range?  (The backbone checks this
-        itself after every call by synchronising the device — here the flag is read once per step, after the step's
-        own event, so that the other lane keeps the device busy.)  Split precision re-calibrates on the images in flight
-        (scales only go down), as IRBackbone._checked does, and the step is run again; plain f16 raises."""
-        ub = self.ub
-        if ub.dtype in ("f16", "f16x2") and ub.range_left(reset=False):
-            if ub.dtype != "f16x2":
-                self.torch.cuda.synchronize(self.device)
-                ub.range_left()
-                raise _abi.AlinkError("activations exceeded the float16 range in this network: build the backbone with dtype='bf16'")
-            self._recalibrate()
-
-    def _recalibrate(self):
-        ub = self.ub
-        self.torch.cuda.synchronize(self.device)
-        ub.range_left()
-        for lane in self.lanes:
-            if lane.active:
-                ub.calibrate(lane.halves[:2 * len(lane.active) * self.group], merge=True)
-        for lane in self.lanes:
-            if lane.active:
-                self._enqueue(lane)
-        self.torch.cuda.synchronize(self.device)
-        if ub.range_left():
-            raise _abi.AlinkError("activations exceeded the float16 range again after re-calibration")
 
     # -- the whole call ----------------------------------------------------------------------------------------------------
     def run(self, make_solver, targets, maxiter, lockstep, verbose=False, early_stop=True):
@@ -255,12 +370,7 @@ class _LockstepEngine(object):
                 s.target_class, s.targeted, s.minimize = targets[i]
                 lane.active.append(s)
 
-        ub = self.ub
-        saved_lazy = getattr(ub, "lazy_range_check", False)
-        if ub.dtype in ("f16", "f16x2"):
-            self.torch.cuda.synchronize(self.device)
-            ub.range_left()
-            ub.lazy_range_check = True
+        self.scorer.begin(self)
         try:
             for lane in lanes:
                 refill(lane)
@@ -273,7 +383,7 @@ class _LockstepEngine(object):
                 if not lane.active:
                     continue
                 lane.done.synchronize()
-                self._range_left()
+                self.scorer.range_left(self)
                 keep = []
                 for j, s in enumerate(lane.active):
                     rows = lane.pred_np[j * self.group:(j + 1) * self.group]
@@ -290,6 +400,7 @@ class _LockstepEngine(object):
                         stop = "maxiter"
                     if stop:
                         results[s.idx] = s.solver.result(s.nit, stop)
+                        results[s.idx].scores = np.array(s.solver.aux[0])      # the best member's own score row
                     else:
                         keep.append(s)
                 lane.active = keep
@@ -297,7 +408,7 @@ class _LockstepEngine(object):
                 if lane.active:
                     self._launch(lane)
         finally:
-            ub.lazy_range_check = saved_lazy
+            self.scorer.end(self)
         return results
 
     def attacked_images(self, results, as_device=False):
@@ -353,9 +464,10 @@ class PixelAttacker:
         return _success(confidence, target_class, targeted_attack, verbose)
 
     def attack(self, image, actual_class, target, pixel_count, dimensions, maxiter=75, popsize=400, verbose=False,
-               seed=None):
+               seed=None, early_stop=True):
         """seed (not in the reference, which seeds nothing: code/attack.py:81-83): this search's own random stream,
-        instead of the attacker's `self.seed` — what makes a pair's search independent of the pairs attacked before it"""
+        instead of the attacker's `self.seed` — what makes a pair's search independent of the pairs attacked before it;
+        early_stop=False: no success test after a generation (attack_all's timing aid)"""
         seed = self.seed if seed is None else seed
         targeted_attack = target is not None
         target_class = target if targeted_attack else actual_class
@@ -371,7 +483,7 @@ class PixelAttacker:
             return self.attack_success(x, image, target_class, targeted_attack, verbose, _scorer=scorer)
 
         attack_result = differential_evolution(predict_fn, bounds, maxiter=maxiter, popsize=popmul, recombination=1,
-                                               atol=-1, callback=callback_fn, polish=False, seed=seed,
+                                               atol=-1, callback=callback_fn if early_stop else None, polish=False, seed=seed,
                                                rng_compat=self.rng_compat)
         self.last_result = attack_result
         attack_image = perturb_image(attack_result.x, image)[0]
@@ -408,11 +520,14 @@ class PixelAttacker:
             if hasattr(input_data, "detach"):                    # the generic route works on host arrays
                 input_data = input_data.detach().cpu().numpy()
             X = []
+            self.last_results = []
             for i, img in enumerate(input_data):
                 target_class = np.argmax(targets[i])
                 result = self.attack(img, 1 - target_class, target_class, pixel_count, dimensions, maxiter=maxiter,
-                                     popsize=popsize, verbose=verbose, seed=None if seeds is None else seeds[i])
+                                     popsize=popsize, verbose=verbose, seed=None if seeds is None else seeds[i],
+                                     early_stop=early_stop)
                 X.append(result)
+                self.last_results.append(self.last_result)
             return X
         if seeds is None:
             from .differential_evolution import _rng_of

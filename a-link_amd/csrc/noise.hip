@@ -571,6 +571,19 @@ __device__ __forceinline__ void src_coord(int d, int src, int dst, int& s0, int&
     w = f;
 }
 
+// The horizontal pass on both rows, then the vertical one:
+//     r0 = a00 * (1 - fx) + a01 * fx,   r1 = a10 * (1 - fx) + a11 * fx,   out = r0 * (1 - fy) + r1 * fy
+// with the roundings PINNED to the ones resize_kernel has always compiled to — each horizontal pass one fused multiply-add onto
+// the rounded first product, the vertical pass two rounded products and an add — because which of two products the compiler
+// contracts into an fma depends on the code around the expression: left to it, perturb_resize_kernel fused the vertical pass,
+// resize_kernel did not, and the two disagreed in the last bit.
+__device__ __forceinline__ float bilinear_taps(float a00, float a01, float a10, float a11, float fx, float fy) {
+#pragma clang fp contract(off)
+    const float r0 = __builtin_fmaf(a01, fx, a00 * (1.f - fx));
+    const float r1 = __builtin_fmaf(a11, fx, a10 * (1.f - fx));
+    return r0 * (1.f - fy) + r1 * fy;
+}
+
 __global__ __launch_bounds__(256) void resize_kernel(const ResizeP p) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long total = (long long)p.N * p.Ho * p.Wo * p.C;
@@ -587,9 +600,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const ResizeP p) {
     const float* im = p.in + (size_t)n * p.H * p.W * p.C;
     const float a00 = im[((size_t)y0 * p.W + x0) * p.C + c], a01 = im[((size_t)y0 * p.W + x1) * p.C + c];
     const float a10 = im[((size_t)y1 * p.W + x0) * p.C + c], a11 = im[((size_t)y1 * p.W + x1) * p.C + c];
-    const float r0 = a00 * (1.f - fx) + a01 * fx;
-    const float r1 = a10 * (1.f - fx) + a11 * fx;
-    p.out[i] = r0 * (1.f - fy) + r1 * fy;
+    p.out[i] = bilinear_taps(a00, a01, a10, a11, fx, fy);
 }
 
 // The adjoint of resize_kernel under the same src_coord rule: din = Ry^T . dout . Rx per image and channel, in the gather form —
@@ -684,6 +695,81 @@ __global__ __launch_bounds__(256) void perturb_kernel(const PerturbP p) {
             d[1] = (float)(long long)x[5 * j + 3];
             d[2] = (float)(long long)x[5 * j + 4];
         }
+    }
+}
+
+// ---- perturb + split + resize in one pass (the few-pixel search against a student that reads Ho x Wo pixels) ---------------
+// dev_out of alink_perturb_images_multi(split = 1) followed by alink_resize_bilinear of each half, bit for bit, without the
+// source-resolution candidates ever existing: 32 searches x 400 candidates x 2 halves at 224 x 224 are 15.4 GB written and read
+// back per generation, the 48 x 48 the student reads 0.71 GB.
+// One workgroup = one candidate.  It PARKS the candidate's k resolved pixels in LDS — position r * W + c in the stacked image
+// (-1: out of range, skipped like perturb_kernel skips it) and the three truncated colours — and the taps of the Ho rows and Wo
+// columns (src_coord itself, once per row / column instead of once per output element: its double division is ~40
+// instructions).  A thread then owns an output PIXEL of one half: four taps, each the base image's value unless the candidate
+// wrote that position — found by a scan of the list from its END (a later entry overwrites an earlier one), which a tap enters
+// only where a 4,096-slot filter of the parked positions says it may hit (40 pixels: 1 % of the slots, so all but ~1 % of the
+// taps cost one LDS byte) — then bilinear_taps.  A half's taps are clamped to the half's own H rows: none crosses the seam.
+// Plain stores, no atomics (filter slots are raced only by stores of the same byte); the partition is fixed, one workgroup per
+// candidate, so the result does not depend on the launch.  Ho == Hc / 2 and Wo == W: every weight is 0, the plain perturb.
+constexpr int PR_KMAX = 128;          // pixels per candidate (the reference's attack uses 40)
+constexpr int PR_TAPS = 512;          // output rows / columns whose taps fit the LDS table
+constexpr int PR_FILTER = 4096;
+struct PerturbResizeP {
+    const float* img;      // [n_img][Hc][W][3]
+    const int* img_of;     // as PerturbP
+    const double* xs;      // [n][5k]
+    float* out;            // [2][n][Ho][Wo][3]
+    int n, k, Hc, W, Ho, Wo, group;
+};
+
+__global__ __launch_bounds__(256) void perturb_resize_kernel(const PerturbResizeP p) {
+    __shared__ int s_pos[PR_KMAX];
+    __shared__ float s_col[PR_KMAX][3];
+    __shared__ unsigned char s_hit[PR_FILTER];
+    __shared__ int s_t0[2][PR_TAPS], s_t1[2][PR_TAPS];       // [0]: rows, [1]: columns
+    __shared__ float s_tw[2][PR_TAPS];
+    const int cand = blockIdx.x, tid = threadIdx.x, H = p.Hc / 2;
+    for (int i = tid; i < PR_FILTER; i += 256) s_hit[i] = 0;
+    for (int i = tid; i < p.Ho + p.Wo; i += 256) {
+        const int ax = i >= p.Ho ? 1 : 0, d = ax ? i - p.Ho : i;
+        int t0, t1;
+        float w;
+        src_coord(d, ax ? p.W : H, ax ? p.Wo : p.Ho, t0, t1, w);
+        s_t0[ax][d] = t0; s_t1[ax][d] = t1; s_tw[ax][d] = w;
+    }
+    __syncthreads();
+    if (tid < p.k) {
+        const double* x = p.xs + ((size_t)cand * p.k + tid) * 5;
+        const long long r = (long long)x[0], c = (long long)x[1];     // astype(int): truncation (perturb_kernel's own)
+        const bool ok = !(r < 0 || r >= p.Hc || c < 0 || c >= p.W);
+        const int pos = ok ? (int)(r * p.W + c) : -1;
+        s_pos[tid] = pos;
+        s_col[tid][0] = (float)(long long)x[2];
+        s_col[tid][1] = (float)(long long)x[3];
+        s_col[tid][2] = (float)(long long)x[4];
+        if (ok) s_hit[pos & (PR_FILTER - 1)] = 1;
+    }
+    __syncthreads();
+    const float* img = p.img + (p.img_of ? (size_t)p.img_of[cand / p.group] * p.Hc * p.W * 3 : 0);
+    const int plane = p.Ho * p.Wo;
+    auto tap = [&](int row, int col, float (&v)[3]) {
+        const int pos = row * p.W + col;
+        const float* s = img + (size_t)pos * 3;
+        v[0] = s[0]; v[1] = s[1]; v[2] = s[2];
+        if (s_hit[pos & (PR_FILTER - 1)]) {
+            for (int j = p.k - 1; j >= 0; --j)
+                if (s_pos[j] == pos) { v[0] = s_col[j][0]; v[1] = s_col[j][1]; v[2] = s_col[j][2]; break; }
+        }
+    };
+    for (int o = tid; o < 2 * plane; o += 256) {
+        const int h = o >= plane ? 1 : 0, q = o - h * plane, oy = q / p.Wo, ox = q - oy * p.Wo;
+        const int y0 = h * H + s_t0[0][oy], y1 = h * H + s_t1[0][oy], x0 = s_t0[1][ox], x1 = s_t1[1][ox];
+        const float fy = s_tw[0][oy], fx = s_tw[1][ox];
+        float a00[3], a01[3], a10[3], a11[3];
+        tap(y0, x0, a00); tap(y0, x1, a01); tap(y1, x0, a10); tap(y1, x1, a11);
+        float* d = p.out + (((size_t)h * p.n + cand) * plane + q) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = bilinear_taps(a00[c], a01[c], a10[c], a11[c], fx, fy);
     }
 }
 
@@ -971,6 +1057,22 @@ int alink_perturb_images_multi(const float* dev_imgs, const int* dev_img_of, int
     if (n == 0) return ALINK_OK;
     PerturbP p{dev_imgs, dev_img_of, dev_xs, dev_out, n, k, Hc, W, split, group};
     hipLaunchKernelGGL(perturb_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+int alink_perturb_resize_multi(const float* dev_imgs, const int* dev_img_of, int group, const double* dev_xs, int n, int k,
+                               int Hc, int W, int Ho, int Wo, float* dev_out, void* stream) {
+    ALINK_REQUIRE(dev_imgs && dev_xs && dev_out && n >= 0 && k >= 0 && Hc > 0 && W > 0 && Ho > 0 && Wo > 0 && group > 0, ALINK_EINVAL,
+                  "bad argument");
+    ALINK_REQUIRE((Hc % 2) == 0, ALINK_EINVAL, "the stacked pair needs an even number of rows, got %d", Hc);
+    ALINK_REQUIRE(k <= PR_KMAX, ALINK_EINVAL, "k=%d pixels per candidate: at most %d", k, PR_KMAX);
+    ALINK_REQUIRE(Ho <= PR_TAPS && Wo <= PR_TAPS, ALINK_EINVAL, "output %d x %d: at most %d x %d", Ho, Wo, PR_TAPS, PR_TAPS);
+    ALINK_REQUIRE((long long)Hc * W < (1ll << 29), ALINK_EINVAL, "stacked pair image too large");
+    DeviceGuard dg(device_of_pointer(dev_out));
+    if (n == 0) return ALINK_OK;
+    PerturbResizeP p{dev_imgs, dev_img_of, dev_xs, dev_out, n, k, Hc, W, Ho, Wo, group};
+    hipLaunchKernelGGL(perturb_resize_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
     ALINK_HIP(hipGetLastError());
     return ALINK_OK;
 }

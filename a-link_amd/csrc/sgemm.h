@@ -31,10 +31,14 @@ struct GemmP {
     int accumulate;           // C += result (after the epilogue terms) instead of C = result
     int splitk, kper;         // grid.z slabs of kper (multiple of 16) reduction steps
     unsigned ci_magic;        // set by launch_gemm32: ceil(2^32 / Ci) (0 for Ci = 1): k / Ci as one multiply-high in the loaders
+    int force_bk;             // 0: the launcher picks the stage depth from the grid (deep()); 16 / 64: this one, whatever the grid —
+                              // with splitk / kper set by the caller, a plan that does not depend on M (gemm32_stage_depth)
 };
 
 void       gemm32_plan_split(GemmP& p, int max_split);
 size_t     gemm32_workspace_floats(const GemmP& p);
+// the stage depth (16 or 64) the launcher picks for a PLANNED p (splitk, kper set) with force_bk == 0
+int        gemm32_stage_depth(const GemmP& p);
 hipError_t launch_gemm32(const GemmP& p, float* workspace, hipStream_t st);
 // out[i] = sum_z part[z][i], i < MN, z < S — the split-K slab sum on its own (fixed order: 8 interleaved groups, then the groups)
 hipError_t launch_slab_sum(const float* part, float* out, long long MN, int S, hipStream_t st);

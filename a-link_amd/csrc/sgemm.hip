@@ -544,7 +544,7 @@ hipError_t launch_v(const GemmP& p, dim3 grid, hipStream_t st) {
 
 template <int AM, int BMo>
 hipError_t launch_t(const GemmP& p, hipStream_t st) {
-    const bool dp = deep(p) && (p.kper % BK_DEEP) == 0;
+    const bool dp = (p.force_bk ? p.force_bk == BK_DEEP : deep(p)) && (p.kper % BK_DEEP) == 0;
     if (narrow(p)) {
         dim3 grid((p.N + 31) / 32, (p.M + 127) / 128, p.splitk);
         const hipError_t e = dp ? launch_v<AM, BMo, 1, BK_DEEP>(p, grid, st) : launch_v<AM, BMo, 1, BK_SMALL>(p, grid, st);
@@ -559,6 +559,8 @@ hipError_t launch_t(const GemmP& p, hipStream_t st) {
 
 }  // namespace
 
+int gemm32_stage_depth(const GemmP& p) { return deep(p) && (p.kper % BK_DEEP) == 0 ? BK_DEEP : BK_SMALL; }
+
 size_t gemm32_workspace_floats(const GemmP& p) { return p.splitk > 1 ? (size_t)p.splitk * p.M * p.ldc : 0; }
 
 // Chooses a split along K so that a small (M, N) problem still fills the chip; kper is a multiple of the stage depth (64).
@@ -572,6 +574,7 @@ void gemm32_plan_split(GemmP& p, int max_split) {
 
 hipError_t launch_gemm32(const GemmP& p, float* workspace, hipStream_t st) {
     if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.splitk < 1 || p.kper <= 0 || (p.kper % BK_SMALL) != 0) return hipErrorInvalidValue;
+    if (p.force_bk != 0 && p.force_bk != BK_SMALL && p.force_bk != BK_DEEP) return hipErrorInvalidValue;
     // the loaders' reciprocal divisions (fdiv) are exact below 2^23
     if ((p.amode == A_CONV && p.M >= (1 << 23)) || (p.amode == A_CONVT && p.K >= (1 << 23)) || p.K >= (1 << 23)) {
         if (p.amode == A_CONV || p.amode == A_CONVT) return hipErrorInvalidValue;

@@ -347,6 +347,13 @@ int run_gemm(alink_smallres* m, GemmP& g, int max_split, hipStream_t st, float* 
     return ALINK_OK;
 }
 
+// The FIXED plan (alink_smallres_score_pairs): split count and stage depth are the ones the planner picks for the layer at a
+// full chunk of 2 MAXN images, whatever the call holds — functions of the layer alone (the tile shape already is: N <= 32).  An
+// output element is one ordered fmaf chain over its slab's k and the slabs are summed in slab order, so under one plan a row
+// has the same bits in every batch and at every position in it.  (The three batch-dependent choices this replaces: small_grid()
+// -> max_split, gemm32_plan_split's tiles * s < 384, deep()'s stage depth by tile count.)
+int run_gemm_fixed(alink_smallres* m, GemmP& g, int rows_per_image, int max_split_small, int max_split_else, hipStream_t st);
+
 // A layer of at most 128 tiles with a long reduction (a small batch's deeper layers: conv4 at 2 x 16 images is 85 tiles x 9 stages on
 // 256 CUs, its input gradient 57 tiles x 9) is split over K: the chip fills, and the slab sum — which applies the epilogue — is one
 // short launch.  Larger grids are not (the slab sum of a 28,800 x 32 output costs more than the split saves: measured).
@@ -355,9 +362,20 @@ inline bool small_grid(const GemmP& g) {
     return (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) <= 128 && g.K >= 512;
 }
 
+int run_gemm_fixed(alink_smallres* m, GemmP& g, int rows_per_image, int max_split_small, int max_split_else, hipStream_t st) {
+    GemmP full = g;
+    full.M = 2 * MAXN * rows_per_image;
+    gemm32_plan_split(full, small_grid(full) ? max_split_small : max_split_else);
+    g.splitk = full.splitk; g.kper = full.kper; g.force_bk = gemm32_stage_depth(full);
+    ALINK_REQUIRE(gemm32_workspace_floats(g) <= m->ws_floats, ALINK_ENOMEM, "sgemm workspace too small (%zu floats)",
+                  gemm32_workspace_floats(g));
+    ALINK_HIP(launch_gemm32(g, m->ws, st));
+    return ALINK_OK;
+}
+
 // out = relu(conv3x3(in, w[layer]) + b[layer]); in is [nb][H][W][Ci]
 int conv_fwd(alink_smallres* m, const float* in, float* out, int layer, int nb, int H, int W, int prescale,
-             hipStream_t st, const float* in2 = nullptr, int split = 0) {
+             hipStream_t st, const float* in2 = nullptr, int split = 0, bool fixed = false) {
     const int Ci = CI[layer], Co = CO[layer], pad = PAD[layer];
     GemmP g{};
     g.A = in; g.A2 = in2; g.a_split = split; g.B = m->d_p + m->oW[layer]; g.C = out;
@@ -365,6 +383,7 @@ int conv_fwd(alink_smallres* m, const float* in, float* out, int layer, int nb, 
     g.M = nb * g.Ho * g.Wo; g.N = Co; g.K = 9 * Ci; g.ldb = Co; g.ldc = Co;
     g.amode = A_CONV; g.bmode = B_ROW; g.H = H; g.W = W; g.Ci = Ci; g.pad = pad; g.prescale = prescale;
     g.bias = m->d_p + m->oB[layer]; g.relu = 1;
+    if (fixed) return run_gemm_fixed(m, g, g.Ho * g.Wo, 4, 1, st);
     return run_gemm(m, g, small_grid(g) ? 4 : 1, st);
 }
 
@@ -372,7 +391,7 @@ int conv_fwd(alink_smallres* m, const float* in, float* out, int layer, int nb, 
 // images from L) — in ONE pass (until round 6: one pass per side; the two sides share every weight, and a layer's launch on
 // 2n images costs what it costs on n: none of them fills the chip); masks == nullptr -> inference (no dropout)
 int tower_fwd(alink_smallres* m, const float* L, const float* R, int n, int prescale, const uint8_t* mask1, const uint8_t* mask2,
-              hipStream_t st, const MaskDraw* draw = nullptr) {
+              hipStream_t st, const MaskDraw* draw = nullptr, bool fixed = false) {
     const float* P = m->d_p;
     const float keep_scale = 1.f / (1.f - 0.25f);
     const int nb = R ? 2 * n : n;
@@ -385,11 +404,11 @@ int tower_fwd(alink_smallres* m, const float* L, const float* R, int n, int pres
         const int mask_blocks = mk.out ? (int)((mk.count + 1023) / 1024) : 0;      // 4 bytes per thread
         hipLaunchKernelGGL(conv1_fwd_kernel, dim3(mk.conv_blocks + mask_blocks), dim3(256), 0, st, c, mk);
     }
-    if ((rc = conv_fwd(m, m->a1, m->a2, 1, nb, m->H, m->W, 0, st))) return rc;
+    if ((rc = conv_fwd(m, m->a1, m->a2, 1, nb, m->H, m->W, 0, st, nullptr, 0, fixed))) return rc;
     hipLaunchKernelGGL(pool_fwd_kernel, g1((long long)nb * m->P1h * m->P1w * 32), dim3(256), 0, st, m->a2, m->p1,
                        m->arg1, mask1, keep_scale, nb, m->H1, m->W1, 32);
-    if ((rc = conv_fwd(m, m->p1, m->a3, 2, nb, m->P1h, m->P1w, 0, st))) return rc;
-    if ((rc = conv_fwd(m, m->a3, m->a4, 3, nb, m->P1h, m->P1w, 0, st))) return rc;
+    if ((rc = conv_fwd(m, m->p1, m->a3, 2, nb, m->P1h, m->P1w, 0, st, nullptr, 0, fixed))) return rc;
+    if ((rc = conv_fwd(m, m->a3, m->a4, 3, nb, m->P1h, m->P1w, 0, st, nullptr, 0, fixed))) return rc;
     hipLaunchKernelGGL(pool_fwd_kernel, g1((long long)nb * m->P2h * m->P2w * 64), dim3(256), 0, st, m->a4, m->p2,
                        m->arg2, mask2, keep_scale, nb, m->H3, m->W3, 64);
     // f = relu(p2 . W + b): [nb][flat] x [flat][feat]
@@ -397,7 +416,7 @@ int tower_fwd(alink_smallres* m, const float* L, const float* R, int n, int pres
     g.A = m->p2; g.B = P + m->oDW; g.C = m->f; g.M = nb; g.N = m->feat; g.K = m->flat;
     g.lda = m->flat; g.ldb = m->feat; g.ldc = m->feat; g.amode = A_ROW; g.bmode = B_ROW;
     g.bias = P + m->oDB; g.relu = 1;
-    if ((rc = run_gemm(m, g, 16, st))) return rc;
+    if ((rc = fixed ? run_gemm_fixed(m, g, 1, 16, 16, st) : run_gemm(m, g, 16, st))) return rc;
     ALINK_HIP(hipGetLastError());
     return ALINK_OK;
 }
@@ -530,6 +549,26 @@ int alink_smallres_forward(alink_smallres_t* m, const float* dev_L, const float*
     int rc = tower_fwd(m, dev_L, dev_R, n, prescale, nullptr, nullptr, st);       // features of L in f[0:n], of R in f[n:2n]
     if (rc) return rc;
     return alink_head_forward(m->head, m->f, m->f + (size_t)n * m->feat, nullptr, nullptr, n, dev_probs, stream);
+}
+
+// Pair scores whose bits do not depend on the batch: the inference forward under the FIXED plan (run_gemm_fixed), any number of
+// pairs, chunked here by MAXN.  The first layer, the pools and the head's one-kernel forward are row-wise already.
+int alink_smallres_score_pairs(alink_smallres_t* m, const float* dev_L, const float* dev_R, int n, int prescale,
+                               float* dev_probs, void* stream) {
+    ALINK_REQUIRE(m && n >= 0, ALINK_EINVAL, "bad argument");
+    if (n == 0) return ALINK_OK;
+    ALINK_REQUIRE(dev_L && dev_R && dev_probs, ALINK_EINVAL, "NULL argument");
+    DeviceGuard dg(m->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t img = (size_t)m->H * m->W * 3;
+    for (int s = 0; s < n; s += MAXN) {
+        const int c = n - s < MAXN ? n - s : MAXN;
+        int rc = tower_fwd(m, dev_L + (size_t)s * img, dev_R + (size_t)s * img, c, prescale, nullptr, nullptr, st, nullptr, true);
+        if (rc) return rc;
+        if ((rc = alink_head_forward(m->head, m->f, m->f + (size_t)c * m->feat, nullptr, nullptr, c, dev_probs + (size_t)s * 2, stream)))
+            return rc;
+    }
+    return ALINK_OK;
 }
 
 int alink_smallres_eval(alink_smallres_t* m, const float* dev_L, const float* dev_R, const float* dev_y, int n,

@@ -342,6 +342,7 @@ class SmallRes(SiameseNetwork, object):
     """code/siamese.py:134-184.  `preprocess` = (x - 128)/128 per side, applied by predict and finetune
     (and by customTrainModel only when preprocess=True, code/siamese.py:88-89)."""
     _identity_preprocess = False
+    _preprocess_is_prescale = True        # `preprocess` is what the kernels' prescale = 1 applies (attack.py's pixel scorer reads this)
 
     def __init__(self, imageShape, featureShape, name, learningRate, seed=None, adadelta_epsilon=1e-8):
         from .smallres import SmallResNet

@@ -145,6 +145,7 @@ class SmallResNet(KerasFitMixin):
         as_torch = isinstance(X[0], self.torch.Tensor)
         L, R = self._dev(X[0]), self._dev(X[1])
         n = L.shape[0]
+        self._check_pairs(L, R)
         out = self.torch.empty((n, 2), dtype=self.torch.float32, device=self.device)
         for s in range(0, n, MAXN):
             m = min(MAXN, n - s)
@@ -152,6 +153,33 @@ class SmallResNet(KerasFitMixin):
                                                        self.prescale, _abi.ptr(out[s:s + m]), _abi.current_stream(self.device)),
                        "alink_smallres_forward")
         return out if as_torch else out.cpu().numpy()
+
+    def _check_pairs(self, L, R):
+        """the kernels read n * H * W * 3 floats of the MODEL's size from each side, whatever the arrays hold (Keras raises here too)"""
+        if L.shape[0] == 0 and R.shape[0] == 0:          # an empty batch reads nothing, whatever shape it arrives in
+            return
+        if tuple(L.shape) != (L.shape[0], self.H, self.W, 3) or tuple(R.shape) != tuple(L.shape):
+            raise ValueError("expected two (n, %d, %d, 3) image batches, got %s and %s" % (self.H, self.W, tuple(L.shape), tuple(R.shape)))
+
+    def score_pairs(self, L, R, out=None, prescale=None):
+        """P(class) of the pairs (L[i], R[i]) as an (n, 2) CUDA float32 tensor (`out`, or a new one) — EXTENSION: the objective of
+        the few-pixel search (attack.py's pixel scorer).  Unlike predict, row i has the same BITS whatever n, whatever chunk of
+        MAXN it falls into and wherever it stands in the call (alink_smallres_score_pairs: every GEMM under a plan that is a
+        function of the layer only), so an image scored among 12,800 candidates scores as it does alone.  Device tensors in and
+        out, any n, enqueued on the current stream of the model's device without synchronising.  prescale (None: this model's
+        own setting) = 1: raw 0..255 pixels, (x - 128) / 128 applied by the first kernel."""
+        torch = self.torch
+        L, R = self._dev(L), self._dev(R)
+        self._check_pairs(L, R)
+        n = L.shape[0]
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (n, 2) or out.dtype is not torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (%d, 2) float32 CUDA tensor" % n)
+        pre = self.prescale if prescale is None else (1 if prescale else 0)
+        _abi.check(self.lib.alink_smallres_score_pairs(self.h, _abi.ptr(L), _abi.ptr(R), n, pre, _abi.ptr(out),
+                                                       _abi.current_stream(self.device)), "alink_smallres_score_pairs")
+        return out
 
     def input_gradients(self, x, y, sample_weight=None, reduction="mean", prescale=None):
         """(dL, dR): the gradient of the Keras loss of the pairs x = [L, R] against the one-hot targets y — the inference forward,

@@ -401,6 +401,15 @@ float* alink_smallres_grads_dev(alink_smallres_t* m);      /* flat tower+head gr
 /* predict: probs (n,2).  n <= 256 per call. */
 int alink_smallres_forward(alink_smallres_t* m, const float* dev_L, const float* dev_R, int n, int prescale,
                            float* dev_probs, void* stream);
+/* EXTENSION (the few-pixel search against the pixel student): the same outputs for ANY n >= 0, chunked inside the call by 256,
+ * asynchronous on `stream`, under a FIXED PLAN: every GEMM of the tower runs with the split count and the stage depth the planner
+ * picks for that layer at a full chunk of 512 images (tile shape 128 x 32 for layers of <= 32 outputs, else 64 x 64) — functions
+ * of the layer alone — and the head's forward is one row-wise kernel.  CONTRACT: row i of dev_probs has the same bits for every
+ * n, every chunk boundary and every position in the call.  (alink_smallres_forward plans by the batch it is given: its bits can
+ * differ from these in the last place.)  Parameters, optimizer state and gradient buffers are untouched; the handle's
+ * activation buffers are overwritten. */
+int alink_smallres_score_pairs(alink_smallres_t* m, const float* dev_L, const float* dev_R, int n, int prescale,
+                               float* dev_probs, void* stream);
 /* one Keras train_on_batch (apply != 0) or gradients only.  dev_masks: the two dropout keep-masks for
  * the 2n tower passes, u8, laid out [2n*P1*P1*32] then [2n*P2*P2*64] (1 = keep), or NULL = no dropout.
  * dev_metrics: {loss, binary_accuracy}. */
@@ -544,6 +553,14 @@ int alink_perturb_images(const float* dev_img, const double* dev_xs, int n, int 
  * candidates [g * group, (g + 1) * group) perturb image dev_img_of[g] (int32, device; NULL: image 0 for all). */
 int alink_perturb_images_multi(const float* dev_imgs, const int* dev_img_of, int group, const double* dev_xs, int n,
                                int k, int Hc, int W, int split, float* dev_out, void* stream);
+/* alink_perturb_images_multi(split = 1) followed by alink_resize_bilinear of each half to (Ho, Wo), bit for bit, in ONE pass that
+ * never materialises a source-resolution candidate (device memory of the call: the image table and dev_out): dev_out is
+ * [2][n][Ho][Wo][3].  Same truncation of coordinates and colours, out-of-range pixels skipped, a later list entry overwrites an
+ * earlier one at the same position; taps and weights by the resize's own rule, each half an image of its own (no tap crosses
+ * the seam).  Ho == Hc / 2 and Wo == W gives the plain perturb.  One workgroup per candidate: the result does not depend on
+ * the launch.  Limits (ALINK_EINVAL beyond): k <= 128 pixels per candidate, Ho and Wo <= 512, Hc even. */
+int alink_perturb_resize_multi(const float* dev_imgs, const int* dev_img_of, int group, const double* dev_xs, int n,
+                               int k, int Hc, int W, int Ho, int Wo, float* dev_out, void* stream);
 /* helpers.augment_data (code/helpers.py:114-141): the affine resampling behind keras_preprocessing's random_rotation /
  * random_shear / random_shift, i.e. scipy.ndimage.affine_transform(channel, A, offset, order, mode='nearest') on every
  * channel, for n_out output images in one launch.  Output i reads image dev_src[i] (int32, device; NULL: image i) of the

@@ -155,6 +155,7 @@ hipError_t launch_conv3x3_c64(int dtype, const ConvParams& p, hipStream_t st);
 hipError_t launch_conv3x3_s2c64(int dtype, const ConvParams& p, hipStream_t st);
 hipError_t c64_set_attributes();
 hipError_t s2c64_set_attributes();
+bool       s2c64_enabled();           // alink_debug_set_s2direct's value
 hipError_t linear_set_attributes();
 hipError_t linear_check_contract();   // probes the LDS out-of-range read contract; disables the linear kernel if it fails
 // front_c64.hip: stem + the first unit's conv1 in one rolling-row launch (the stem's activation stays in LDS; the quarter
@@ -167,6 +168,13 @@ hipError_t launch_front_c64(int dtype, const ConvParams& conv1, const StemParams
 bool       unit_c64_applies(int dtype, const ConvParams& c1, const ConvParams& c2);
 hipError_t unit_c64_set_attributes();
 hipError_t launch_unit_c64(int dtype, const ConvParams& c1, const ConvParams& c2, hipStream_t st);
+// unit1_c64.hip: the stem and the whole first unit (conv1 + PReLU, stride-2 conv2 + projection shortcut) in one rolling-row
+// launch; c1 / stem as launch_front_c64 would get them, c2 as launch_conv3x3_s2c64 would in its shortcut form (neither
+// c1.out nor c2.in2 is touched).  unit1_c64_mode: alink_debug_set_fuse_unit1's value
+bool       unit1_c64_applies(int dtype, const ConvParams& c1, const StemParams& stem, const ConvParams& c2);
+int        unit1_c64_mode();
+hipError_t unit1_c64_set_attributes();
+hipError_t launch_unit1_c64(int dtype, const ConvParams& c1, const StemParams& stem, const ConvParams& c2, bool slopes_le_1, hipStream_t st);
 // conv3x3_lat.hip: the latency form for launches of a handful of images (one wave per 32 x 32 output block, operands straight from L2)
 bool       conv3x3_lat_applies(int dtype, const ConvParams& p);
 hipError_t launch_conv3x3_lat(int dtype, const ConvParams& p, hipStream_t stream);

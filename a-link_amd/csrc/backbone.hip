@@ -812,6 +812,22 @@ static const ConvLayer* fusable_unit(const alink_backbone* bb, const ConvLayer& 
     return &L2;
 }
 
+// The stem and the whole first unit as one launch (unit1_c64.hip) where the fused front kernel and the direct stride-2
+// kernel would run today: alink_debug_set_fuse_unit1 0 = off, 1 = from FUSE_UNIT1_MIN_N images per launch, 2 = at every
+// batch size.  A workgroup's range is N * 56 / 256 output rows and starts with nine passes that fill the three rings (about
+// two output rows' worth of work); at 64 images a range is 14 rows, below that the fill outweighs the saved round trip, as
+// for the plain units.
+constexpr int FUSE_UNIT1_MIN_N = 64;
+static bool fusable_unit1(const alink_backbone* bb, bool front, int N, bool cache) {
+    const int mode = unit1_c64_mode();
+    if (!front || !mode || (mode == 1 && N < FUSE_UNIT1_MIN_N) || cache || g_ablate || g_stamps || !s2c64_enabled()) return false;
+    const ConvLayer& L = bb->convs[0];
+    const ConvLayer& L2 = bb->convs[1];
+    if (L.role != 1 || L2.role != 3 || L2.unit != L.unit || L2.in_buf != L.out_buf || L2.resid_buf >= 0) return false;
+    if (L2.kernel != ConvKernel::Roll112S2 || L2.Cin2 != 64 || L2.in2_buf != 0 || L2.Cout != 64) return false;
+    return plan_split(bb, L2, N) == 1;
+}
+
 // calib (ALINK_DT_F16X2 only): 0 = a normal forward; 1 = choose every tensor's scale exponent from this batch; 2 = the
 // same, never above the exponents already held (re-calibration after a batch left the range).  Synchronous when != 0.
 static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int N, float* dev_out,
@@ -966,6 +982,26 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             });
             if (rc) return rc;
             bexp[L.out_buf] = L.e_out;
+        } else if (front && &L == &bb->convs[0] && fusable_unit1(bb, front, N, cache != nullptr)) {
+            // stem, conv1, conv2 + shortcut in one launch (unit1_c64.hip): neither t nor the shortcut's operand is written
+            const ConvLayer& L2 = bb->convs[1];
+            ConvParams p2 = p;
+            p2.in = buf(L2.in_buf); p2.wgt = L2.d_w; p2.bias = L2.d_bias; p2.alpha = L2.d_alpha; p2.resid = nullptr;
+            p2.out = buf(L2.out_buf); p2.Cout = L2.Cout; p2.Ho = L2.Hout; p2.Wo = L2.Wout; p2.stride = L2.stride;
+            p2.M = N * L2.Hout * L2.Wout; p2.border_cls = L2.border_cls ? 1 : 0;
+            p2.in2 = buf(L2.in2_buf); p2.Cin2 = L2.Cin2; p2.in2_compact = 1;
+            p2.ksteps_per_split = L2.ksz * L2.ksz * (L2.Cin / 64) + L2.Cin2 / 64;
+            ALINK_REQUIRE(unit1_c64_applies(cfg.dtype, p, sp, p2), ALINK_EINVAL, "fused unit %s: launch forms do not apply", L.name.c_str());
+            for (int r = 0; r < reps; ++r) ALINK_HIP(launch_unit1_c64(cfg.dtype, p, sp, p2, bb->front_slopes_le_1, stream));
+            // one profile entry per layer, as for the plain fused units: conv1 (+ stem) and conv2 (+ shortcut), half the time each
+            note(conv_flops(p) + 2.0 * N * cfg.height * cfg.width * 64.0 * 27.0, 1);
+            if ((rc = mark())) return rc;
+            if (prof && nl < cap) split_pairs.push_back(nl - 1);
+            note(conv_flops(p2), 1);
+            if ((rc = mark())) return rc;
+            last_out = L2.out_buf;
+            skip_conv2 = true;
+            continue;
         } else if (front && &L == &bb->convs[0]) {
             p.stamps = g_stamps;
             for (int r = 0; r < reps; ++r) ALINK_HIP(launch_front_c64(cfg.dtype, p, sp, buf(0), bb->front_slopes_le_1, stream));

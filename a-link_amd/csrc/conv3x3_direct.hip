@@ -399,6 +399,7 @@ hipError_t direct_set_attributes() {
     if ((e = front_c64_set_attributes()) != hipSuccess) return e;
     if ((e = s2c64_set_attributes()) != hipSuccess) return e;
     if ((e = unit_c64_set_attributes()) != hipSuccess) return e;
+    if ((e = unit1_c64_set_attributes()) != hipSuccess) return e;
     return linear_set_attributes();
 }
 

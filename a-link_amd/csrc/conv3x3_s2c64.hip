@@ -228,6 +228,7 @@ bool g_use_s2c64 = true;
 }  // namespace
 
 extern "C" void alink_debug_set_s2direct(int on) { g_use_s2c64 = on != 0; }
+bool s2c64_enabled() { return g_use_s2c64; }
 
 // the direct stride-2 kernel for 112 x 112 x 64 -> 56 x 56 x 64 (ConvKernel::Igemm = not applicable)
 ConvKernel s2c64_variant(int ksz, int stride, int pad, int H, int W, int Cin, int Cout) {

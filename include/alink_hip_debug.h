@@ -39,6 +39,11 @@ void alink_debug_set_fuse_stem(int on);
 /* plain 56 x 56 x 64 residual units (stage 1) in one launch, conv1's output kept in LDS (unit_c64.hip; 16-bit forward only):
  * 0 = never (two conv3x3_linear launches), 1 = from the batch size the dispatch picks (default), 2 = at every batch size */
 void alink_debug_set_fuse_unit(int mode);
+/* the stem and the whole of stage1_unit1 (conv1, stride-2 conv2 + shortcut) in one launch, neither conv1's output nor the
+ * shortcut's operand leaving LDS (unit1_c64.hip; 16-bit inference forward at 112 x 112 only): 0 = never (the fused front
+ * kernel + the direct stride-2 kernel), 1 = from the batch size the dispatch picks (default), 2 = at every batch size.
+ * alink_debug_set_fuse_stem(0) and alink_debug_set_s2direct(0) each turn it off as well. */
+void alink_debug_set_fuse_unit1(int mode);
 /* 0: projection shortcuts as launches of their own instead of extra K-steps of conv2.  READ AT alink_backbone_create. */
 void alink_debug_set_fuse_shortcut(int on);
 /* 0: the implicit GEMM stages its tiles through registers (global_load -> ds_write) instead of LDS-DMA */

@@ -25,6 +25,7 @@ ap.add_argument("--lib", default="", help="experiments: load this build of libal
 ap.add_argument("--no-s2direct", action="store_true", help="A/B: stage1_unit1's stride-2 conv2 + shortcut on the implicit-GEMM kernel")
 ap.add_argument("--no-fuse-sc", action="store_true", help="A/B: projection shortcuts as launches of their own")
 ap.add_argument("--no-fuse-unit", action="store_true", help="A/B: plain stage-1 units as two linear-tile launches instead of one (unit_c64.hip)")
+ap.add_argument("--no-fuse-unit1", action="store_true", help="A/B: stem + stage1_unit1 as the fused front kernel + the direct stride-2 kernel instead of one launch (unit1_c64.hip)")
 ap.add_argument("--linear", type=int, default=-1, help="linear-tile widths: bit0 56, bit1 28, bit2 14, bit3 7 (default: library default)")
 a = ap.parse_args()
 units = W.ARCH_UNITS[a.model]
@@ -43,6 +44,8 @@ if a.no_fuse_sc:
     _lib.alink_debug_set_fuse_shortcut(0)
 if a.no_fuse_unit:
     _lib.alink_debug_set_fuse_unit(0)
+if a.no_fuse_unit1:
+    _lib.alink_debug_set_fuse_unit1(0)
 if a.no_c64:
     _lib.alink_debug_set_c64(0)
 if a.no_fuse_stem:

@@ -12,6 +12,8 @@ one fused perturb + split + resize launch (attack.py's pixel scorer; all the sea
 --attack_pixels 40, --attack_maxiter 50, --attack_popsize 250, the reference's (code/attack.py:91) — are options of this driver.
 --noise also takes the gradient extensions `fgsm` / `pgd`: with feature_model=None they attack the student on the pixels the
 driver perturbs (noise.FGSM's pixel-model route: SmallRes.input_gradients, pulled back through the resize to lowRes).
+--gallery_eval (an extension, off by default) computes the closing top-1 identification with every test face embedded once
+(SmallRes.identify) instead of once per (probe, gallery) pair, and adds the rank-1 / CMC figures on P(same).
 """
 import argparse
 import sys
@@ -39,6 +41,8 @@ def build_parser():
     p.add_argument("--attack_pixels", type=int, default=40)
     p.add_argument("--attack_maxiter", type=int, default=50)
     p.add_argument("--attack_popsize", type=int, default=250)
+    # EXTENSION, off: the closing top-1 identification with every test face embedded once (alink_loop.top1_identification_gallery)
+    p.add_argument("--gallery_eval", action="store_true", default=False)
     return p
 
 
@@ -85,8 +89,15 @@ def main(argv=None):
     state = alink_loop.run_alink_mtp(FLAGS, conversionModel, bag, ensembleNoise, lowResModel, X_dig_post, dataGen,
                                      IMAGE_RES, low_res, verbose=verbose)
     X_test = readMTP.readAllImages(FLAGS.testDir, low_res)
-    state.top1 = alink_loop.top1_identification(lowResModel, X_test)
+    if FLAGS.gallery_eval:
+        det = {}
+        state.top1 = alink_loop.top1_identification_gallery(lowResModel, X_test, details=det)
+        state.identification = alink_loop.identification_stats(det["best"], det["rank"], det["true_ids"])
+    else:
+        state.top1 = alink_loop.top1_identification(lowResModel, X_test)
     print('Top-1 accuracy : ', state.top1)
+    if FLAGS.gallery_eval:
+        print('Rank-1 on P(same) (extension) : ', state.identification["rank1"], ' CMC : ', state.identification["cmc"])
     return state
 
 

@@ -103,6 +103,7 @@ PROTOTYPES = {
     "alink_committee_forward": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "alink_committee_forward_multi": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i64, _vp, _vp]),
     "alink_pair_scores_matrix": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "alink_head_forward_rect": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "alink_roc_counts": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "alink_head_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
     "alink_head_apply_update": (_i, [_vp, _vp]),
@@ -122,6 +123,8 @@ PROTOTYPES = {
     "alink_smallres_grads_dev": (_vp, [_vp]),
     "alink_smallres_forward": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "alink_smallres_score_pairs": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "alink_smallres_features": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "alink_smallres_score_features": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "alink_smallres_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp]),
     "alink_smallres_train_step_drawn": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_uint64, _f, _i, _vp, _vp]),
     "alink_smallres_train_on_batch_host": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_uint64, _vp, _vp]),
@@ -154,6 +157,7 @@ PROTOTYPES = {
     "alink_score": (_i, [_i, _vp, _vp, _i, _i64, _i, _vp, _vp]),
     "alink_topk_scratch_bytes": (_sz, [_i64, _i]),
     "alink_topk": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "alink_identify_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -622,6 +622,44 @@ def top1_identification(lowResModel, X_test, chunk_pairs=8192):
     return acc / float(len(probes))
 
 
+def _gallery_split(X_test):
+    """(probes, person id of every probe, gallery) of the reference's test protocol (code/ALINK_MTP.py:275-281): the gallery is every
+    person's first image, every image — the gallery ones included — is a probe"""
+    gallery = np.stack([np.asarray(x[0]) for x in X_test])
+    probes = np.stack([np.asarray(x) for person in X_test for x in person])
+    ids = np.asarray([i for i, person in enumerate(X_test) for _ in person], dtype=np.int32)
+    return probes, ids, gallery
+
+
+def top1_identification_gallery(lowResModel, X_test, max_scores_bytes=64 << 20, details=None):
+    """code/ALINK_MTP.py:274-289 with every face embedded ONCE (lowResModel.identify: P + G tower passes, the pair head on the
+    P x G feature pairs and each probe's argmax on the device) instead of the tower on 2 P G pair occurrences.  The same
+    accuracy formula on the same index: the argmax of the probe's (G, 2) scores FLATTENED is compared with the person id, as the
+    reference does.  The scores are score_pairs' (a plan fixed per layer), predict's are planned by the batch: the last bits can
+    differ, so this is not what the drivers call by default (ALINK_MTP --gallery_eval).  `details` (a dict) receives identify's
+    arrays and the probes' person ids (for identification_stats)."""
+    probes, ids, gallery = _gallery_split(X_test)
+    got = lowResModel.identify(probes, gallery, true_ids=ids, col=1, max_scores_bytes=max_scores_bytes)
+    if details is not None:
+        details.update(got, true_ids=ids, gallery_size=len(gallery))
+    return int(np.sum(got["flat_argmax"] == ids)) / float(len(ids))
+
+
+def identification_stats(best, rank, true_ids, ks=(1, 5, 10)):
+    """EXTENSION (host only; not in the reference, whose one number is the flattened-argmax accuracy above): closed-set
+    identification figures on P(same) — column 1 — from SmallRes.identify's `best` and `rank` arrays.
+      "rank1": the share of probes whose highest-scoring gallery face (`best`: ties towards the lower index) is their own;
+      "cmc": {k: the share of probes whose own gallery face is among the k best (rank < k; a stable descending sort)}
+             — the cumulative match characteristic; cmc[1] == rank1 when every probe's person is in the gallery.
+    A probe whose person is not in the gallery (rank -1) counts as a miss at every k."""
+    best, rank, true_ids = (np.asarray(a).reshape(-1) for a in (best, rank, true_ids))
+    if not (len(best) == len(rank) == len(true_ids)):
+        raise ValueError("best, rank and true_ids must have one entry per probe")
+    n = float(max(len(best), 1))
+    return {"rank1": float(np.sum(best == true_ids)) / n,
+            "cmc": {int(k): float(np.sum((rank >= 0) & (rank < int(k)))) / n for k in ks}}
+
+
 def pretrain(model, dataGen, epochs, batch_size, n_steps=320000, refine=False, verbose=1):
     """The pre-training branches of the drivers (code/ALINK_arc.py:96-137): load if saved, else (or
     when refining) customTrainModel on the balanced generator and save.  Returns True if trained."""

@@ -118,7 +118,7 @@ struct HeadFwd {
     int D, h1, h2;
     int accumulate;     // add to probs already there (committee member > 0)
     float final_div;    // > 0: divide by it after adding (last committee member)
-    int matN;           // > 0: score-matrix mode, pair p = (mat_row0 + p / matN, p % matN) of one matrix L == R
+    int matN;           // > 0: score-matrix mode, pair p = (L row mat_row0 + p / matN, R row p % matN); L == R: the square matrix
     int mat_row0;
     int out_col;        // >= 0: write only this softmax column, probs is [P] (else [P][od])
     int od;             // 2: softmax over Dense(2); 1: sigmoid of Dense(1)
@@ -2121,6 +2121,22 @@ int alink_pair_scores_matrix(alink_head_t* const* heads, int n_heads, const floa
         if (rc) return rc;
     }
     return ALINK_OK;
+}
+
+// The rectangular form of the score matrix: pair p = (p / nR, p % nR) of TWO matrices, enumerated by head_fwd_kernel (the
+// kernel alink_head_forward launches for an f32 head: a pair's bits are the ones it has there).
+int alink_head_forward_rect(alink_head_t* h, const float* dev_L, int nL, const float* dev_R, int nR, int col,
+                            float* dev_scores, void* stream) {
+    ALINK_REQUIRE(h && nL >= 0 && nR >= 0, ALINK_EINVAL, "bad argument");
+    ALINK_REQUIRE(col >= -1 && col < h->od, ALINK_EINVAL, "col=%d outside -1 .. %d", col, h->od - 1);
+    ALINK_REQUIRE((long long)nL * nR * h->od <= ALINK_HEAD_RECT_MAX_SCORES, ALINK_EINVAL,
+                  "%d x %d x %d scores exceed the %lld of one call: walk the rows in blocks", nL, nR, h->od,
+                  (long long)ALINK_HEAD_RECT_MAX_SCORES);
+    if (nL == 0 || nR == 0) return ALINK_OK;
+    ALINK_REQUIRE(dev_L && dev_R && dev_scores, ALINK_EINVAL, "NULL argument");
+    DeviceGuard dg(h->device);
+    return launch_fwd(h, dev_L, dev_R, nullptr, nullptr, (long long)nL * nR, dev_scores, 0, 0.f, (hipStream_t)stream, nR, 0,
+                      h->od == 1 ? -1 : col);
 }
 
 static int train_step_launches(alink_head_t* h, const float* dev_L, const float* dev_R, const float* dev_y,

@@ -9,6 +9,9 @@
 // ties break towards the lower index deterministically — the reference's np.argsort/argpartition
 // tie order is unspecified), then a bitonic sort of just the k survivors.  Each select pass streams
 // the P keys once (8 B/key), histogramming in LDS.
+//
+// alink_identify_rows replaces the per-probe np.argmax of code/ALINK_MTP.py:285 over a whole (P, G, C) score array: one
+// workgroup per probe row, wave reductions, no atomics.
 #include "alink_common.h"
 
 namespace alink {
@@ -179,6 +182,69 @@ __global__ void emit_kernel(const unsigned long long* __restrict__ keys, const f
     if (vals) vals[i] = scores[id];
 }
 
+// ---- identification: one row reduction per probe over a (P, G, C) score array (code/ALINK_MTP.py:285-287) -----------------
+// A candidate is (value, index); `a` yields to `b` when b is strictly larger, or equal with the lower index: the first maximum
+// of the row whatever order the candidates meet in.  A NaN compares false both ways and never enters.
+struct IdCand { float v; int i; };
+__device__ __forceinline__ IdCand id_better(IdCand a, IdCand b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
+__device__ __forceinline__ IdCand id_wave_max(IdCand a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        IdCand b;
+        b.v = __shfl_xor(a.v, o, 64);
+        b.i = __shfl_xor(a.i, o, 64);
+        a = id_better(a, b);
+    }
+    return a;
+}
+__device__ __forceinline__ int id_wave_sum(int c) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    return c;
+}
+constexpr int ID_NONE = 0x7fffffff;   // index of a candidate that has seen nothing larger than -inf
+
+// workgroup = a probe row (grid-strided over the rows), thread = gallery entries tid, tid + 256, ...: ascending inside a thread,
+// so `>` keeps a thread's first maximum; waves reduce by lane exchange, the four wave results meet in LDS.
+__global__ __launch_bounds__(256) void identify_rows_kernel(const float* __restrict__ scores, int P, int G, int C, int col,
+                                                            const int32_t* __restrict__ truth, int32_t* __restrict__ flat_argmax,
+                                                            int32_t* __restrict__ best, int32_t* __restrict__ rank) {
+    __shared__ IdCand s_flat[4], s_best[4];
+    __shared__ int s_cnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int p = blockIdx.x; p < P; p += gridDim.x) {
+        const float* row = scores + (size_t)p * G * C;
+        const int t = (rank && truth) ? truth[p] : -1;
+        const bool ranked = t >= 0 && t < G;                       // (uniform over the workgroup)
+        const float tv = ranked ? row[(size_t)t * C + col] : 0.f;   // never read outside the row
+        IdCand f{-INFINITY, ID_NONE}, b{-INFINITY, ID_NONE};
+        int cnt = 0;
+        for (int g = tid; g < G; g += 256) {
+            const float* e = row + (size_t)g * C;
+            for (int c = 0; c < C; ++c) {
+                const float v = e[c];
+                if (v > f.v) { f.v = v; f.i = g * C + c; }
+            }
+            const float v = e[col];
+            if (v > b.v) { b.v = v; b.i = g; }
+            cnt += (ranked && (v > tv || (v == tv && g < t))) ? 1 : 0;
+        }
+        f = id_wave_max(f);
+        b = id_wave_max(b);
+        cnt = id_wave_sum(cnt);
+        if (lane == 0) { s_flat[wave] = f; s_best[wave] = b; s_cnt[wave] = cnt; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w) { f = id_better(f, s_flat[w]); b = id_better(b, s_best[w]); cnt += s_cnt[w]; }
+            // nothing above -inf in the row (all -inf / NaN): index 0, np.argmax's answer for a constant row
+            if (flat_argmax) flat_argmax[p] = f.i == ID_NONE ? 0 : f.i;
+            if (best) best[p] = b.i == ID_NONE ? 0 : b.i;
+            if (rank) rank[p] = ranked ? cnt : -1;
+        }
+        __syncthreads();                                           // the LDS slots are free for the next row
+    }
+}
+
 unsigned int next_pow2(unsigned int x) {
     unsigned int p = 1;
     while (p < x) p <<= 1;
@@ -204,6 +270,21 @@ int alink_score(int kind, const float* dev_probs, const float* dev_b, int col, i
     ALINK_REQUIRE(P > 0, ALINK_EINVAL, "negative P");
     hipLaunchKernelGGL(score_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, kind,
                        dev_probs, dev_b, col, (long long)P, C, dev_scores);
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+int alink_identify_rows(const float* dev_scores, int P, int G, int C, int col, const int32_t* dev_true,
+                        int32_t* dev_flat_argmax, int32_t* dev_best, int32_t* dev_rank, void* stream) {
+    ALINK_REQUIRE(P >= 0 && G >= 1 && C >= 1 && col >= 0 && col < C, ALINK_EINVAL, "bad shape (P=%d, G=%d, C=%d, col=%d)", P, G, C, col);
+    ALINK_REQUIRE((long long)G * C < (1ll << 31), ALINK_EINVAL, "G * C = %lld does not fit the int32 flattened index", (long long)G * C);
+    ALINK_REQUIRE(!dev_rank || dev_true, ALINK_EINVAL, "dev_rank needs dev_true");
+    if (P == 0 || (!dev_flat_argmax && !dev_best && !dev_rank)) return ALINK_OK;
+    ALINK_REQUIRE(dev_scores, ALINK_EINVAL, "NULL scores");
+    DeviceGuard dg(device_of_pointer(dev_scores));
+    const unsigned blocks = P < 65536 ? (unsigned)P : 65536u;     // the kernel strides over the rows
+    hipLaunchKernelGGL(identify_rows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dev_scores, P, G, C, col, dev_true,
+                       dev_flat_argmax, dev_best, dev_rank);
     ALINK_HIP(hipGetLastError());
     return ALINK_OK;
 }

@@ -391,7 +391,7 @@ int conv_fwd(alink_smallres* m, const float* in, float* out, int layer, int nb, 
 // images from L) — in ONE pass (until round 6: one pass per side; the two sides share every weight, and a layer's launch on
 // 2n images costs what it costs on n: none of them fills the chip); masks == nullptr -> inference (no dropout)
 int tower_fwd(alink_smallres* m, const float* L, const float* R, int n, int prescale, const uint8_t* mask1, const uint8_t* mask2,
-              hipStream_t st, const MaskDraw* draw = nullptr, bool fixed = false) {
+              hipStream_t st, const MaskDraw* draw = nullptr, bool fixed = false, float* f_out = nullptr) {
     const float* P = m->d_p;
     const float keep_scale = 1.f / (1.f - 0.25f);
     const int nb = R ? 2 * n : n;
@@ -411,9 +411,9 @@ int tower_fwd(alink_smallres* m, const float* L, const float* R, int n, int pres
     if ((rc = conv_fwd(m, m->a3, m->a4, 3, nb, m->P1h, m->P1w, 0, st, nullptr, 0, fixed))) return rc;
     hipLaunchKernelGGL(pool_fwd_kernel, g1((long long)nb * m->P2h * m->P2w * 64), dim3(256), 0, st, m->a4, m->p2,
                        m->arg2, mask2, keep_scale, nb, m->H3, m->W3, 64);
-    // f = relu(p2 . W + b): [nb][flat] x [flat][feat]
+    // f = relu(p2 . W + b): [nb][flat] x [flat][feat]  (f_out: into the caller's feature matrix instead — alink_smallres_features)
     GemmP g{};
-    g.A = m->p2; g.B = P + m->oDW; g.C = m->f; g.M = nb; g.N = m->feat; g.K = m->flat;
+    g.A = m->p2; g.B = P + m->oDW; g.C = f_out ? f_out : m->f; g.M = nb; g.N = m->feat; g.K = m->flat;
     g.lda = m->flat; g.ldb = m->feat; g.ldc = m->feat; g.amode = A_ROW; g.bmode = B_ROW;
     g.bias = P + m->oDB; g.relu = 1;
     if ((rc = fixed ? run_gemm_fixed(m, g, 1, 16, 16, st) : run_gemm(m, g, 16, st))) return rc;
@@ -569,6 +569,31 @@ int alink_smallres_score_pairs(alink_smallres_t* m, const float* dev_L, const fl
             return rc;
     }
     return ALINK_OK;
+}
+
+// The tower alone, an image at a time (gallery identification: P + G tower passes instead of 2 P G): chunks of 2 MAXN images —
+// what the activation buffers hold — through the layers score_pairs runs, under the same FIXED plan, so a face has the bits it
+// has there; the last GEMM writes the chunk's rows straight into the caller's matrix.
+int alink_smallres_features(alink_smallres_t* m, const float* dev_images, int n, int prescale, float* dev_feat, void* stream) {
+    ALINK_REQUIRE(m && n >= 0, ALINK_EINVAL, "bad argument");
+    if (n == 0) return ALINK_OK;
+    ALINK_REQUIRE(dev_images && dev_feat, ALINK_EINVAL, "NULL argument");
+    DeviceGuard dg(m->device);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t img = (size_t)m->H * m->W * 3;
+    for (int s = 0; s < n; s += 2 * MAXN) {
+        const int c = n - s < 2 * MAXN ? n - s : 2 * MAXN;
+        const int rc = tower_fwd(m, dev_images + (size_t)s * img, nullptr, c, prescale, nullptr, nullptr, st, nullptr, true,
+                                 dev_feat + (size_t)s * m->feat);
+        if (rc) return rc;
+    }
+    return ALINK_OK;
+}
+
+int alink_smallres_score_features(alink_smallres_t* m, const float* dev_L, int nL, const float* dev_R, int nR, int col,
+                                  float* dev_scores, void* stream) {
+    ALINK_REQUIRE(m, ALINK_EINVAL, "NULL model");
+    return alink_head_forward_rect(m->head, dev_L, nL, dev_R, nR, col, dev_scores, stream);
 }
 
 int alink_smallres_eval(alink_smallres_t* m, const float* dev_L, const float* dev_R, const float* dev_y, int n,

@@ -368,6 +368,46 @@ class SmallRes(SiameseNetwork, object):
         (SmallResNet.input_gradients with prescale: no host pass over the pixels)."""
         return self.siamese_net.input_gradients(X, Y, sample_weight=sample_weight, reduction=reduction, prescale=True)
 
+    def identify(self, probes, gallery, true_ids=None, col=1, max_scores_bytes=64 << 20):
+        """EXTENSION: every probe against every gallery face (RAW 0..255 pixels, what predict takes; `preprocess` applied by the
+        first kernel) with each face embedded ONCE — the identification loop of code/ALINK_MTP.py:279-288 runs the tower on the
+        probe and on the whole gallery again for every probe (2 P G tower passes; here P + G).  The gallery's features are
+        computed once; the probes are walked in chunks sized so that a chunk's (rows, G, 2) score block stays under
+        `max_scores_bytes` (at least one probe per chunk), and no more than one chunk of probe features and scores is on the
+        device at a time.  Returns a dict of NumPy int32 arrays of length P (smallres.identify_rows):
+          "flat_argmax": np.argmax of the probe's (G, 2) scores flattened — the reference's predicted_id, its quirk included;
+          "best": the lowest gallery index maximising column `col` (1 = P(same));
+          "rank" (only with true_ids): the place of gallery true_ids[p] in a stable descending sort of column `col`, -1 where
+          true_ids[p] is no gallery index.
+        Scored under score_pairs' fixed plan: the bits of smallres.SmallResNet.score_pairs on the materialised pairs, which can
+        differ from predict's in the last place."""
+        from . import smallres as _sr
+        net = self.siamese_net
+        torch = net.torch
+        P, G = len(probes), len(gallery)
+        if G < 1:
+            raise ValueError("identify needs at least one gallery image")
+        tid = None if true_ids is None else np.asarray(true_ids, dtype=np.int32).reshape(-1)
+        if tid is not None and tid.size != P:
+            raise ValueError("true_ids must hold one gallery index per probe (%d), got %d" % (P, tid.size))
+        take = (lambda a, s, e: a[s:e]) if hasattr(probes, "shape") else (lambda a, s, e: np.stack([np.asarray(x) for x in a[s:e]]))
+        FG = net.features(gallery if hasattr(gallery, "shape") else np.stack([np.asarray(x) for x in gallery]), prescale=True)
+        rows = int(max(1, min(int(max_scores_bytes) // (G * 2 * 4), (1 << 28) // (G * 2), max(P, 1))))
+        feat = torch.empty((rows, net.feat), dtype=torch.float32, device=net.device)
+        scores = torch.empty((rows, G, 2), dtype=torch.float32, device=net.device)
+        outs = []
+        for s in range(0, P, rows):
+            c = min(rows, P - s)
+            net.features(take(probes, s, s + c), out=feat[:c], prescale=True)
+            net.score_matrix(feat[:c], FG, col=-1, out=scores[:c])
+            outs.append(_sr.identify_rows(scores[:c], col=col, true_ids=None if tid is None else tid[s:s + c]))
+        res = {}
+        for k, name in enumerate(("flat_argmax", "best", "rank")):
+            if name == "rank" and tid is None:
+                continue
+            res[name] = torch.cat([o[k] for o in outs]).cpu().numpy() if outs else np.zeros(0, np.int32)
+        return res
+
 
 class FaceVGG16:
     """code/siamese.py:187-200: VGGFace VGG-16 pool5 features (25088-d at 224 x 224).  `weights`: path of

@@ -18,6 +18,38 @@ MAXN = 256
 _NO_CONTEXT = contextlib.nullcontext()
 
 
+def identify_rows(scores, col=1, true_ids=None):
+    """(flat_argmax, best, rank) of a (P, G, C) — or (P, G): one column — CUDA float32 score array, one row reduction per probe on
+    the device (alink_identify_rows), as int32 CUDA tensors of length P; nothing synchronises.
+      flat_argmax[p]: np.argmax of the row flattened to G * C — the index the reference compares with the person id
+                      (code/ALINK_MTP.py:285-287);
+      best[p] (EXTENSION): the lowest g maximising scores[p][g][col];
+      rank[p] (EXTENSION; None without true_ids): the 0-based place of gallery true_ids[p] in a stable descending sort of
+                      column col, -1 where true_ids[p] is outside 0 .. G - 1."""
+    import torch
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype is torch.float32 and scores.is_contiguous()
+            and scores.dim() in (2, 3)):
+        raise ValueError("scores must be a contiguous (P, G, C) or (P, G) float32 CUDA tensor")
+    P, G = int(scores.shape[0]), int(scores.shape[1])
+    Cn = int(scores.shape[2]) if scores.dim() == 3 else 1
+    dev = scores.device
+    lib = _abi.init(dev.index)
+    flat = torch.empty(P, dtype=torch.int32, device=dev)
+    best = torch.empty(P, dtype=torch.int32, device=dev)
+    rank = true = None
+    if true_ids is not None:
+        if isinstance(true_ids, torch.Tensor):
+            true = true_ids.to(dev, torch.int32).reshape(-1).contiguous()
+        else:
+            true = torch.from_numpy(np.ascontiguousarray(true_ids, dtype=np.int32).reshape(-1)).to(dev)
+        if true.numel() != P:
+            raise ValueError("true_ids must hold one gallery index per probe (%d), got %d" % (P, true.numel()))
+        rank = torch.empty(P, dtype=torch.int32, device=dev)
+    _abi.check(lib.alink_identify_rows(_abi.ptr(scores), P, G, Cn, int(col), _abi.ptr(true), _abi.ptr(flat), _abi.ptr(best),
+                                       _abi.ptr(rank), _abi.current_stream(dev)), "alink_identify_rows")
+    return flat, best, rank
+
+
 class SmallResNet(KerasFitMixin):
     def __init__(self, image_shape, feat, lr=1.0, rho=0.95, eps=1e-8, seed=None, device=None, prescale=False):
         import torch
@@ -179,6 +211,48 @@ class SmallResNet(KerasFitMixin):
         pre = self.prescale if prescale is None else (1 if prescale else 0)
         _abi.check(self.lib.alink_smallres_score_pairs(self.h, _abi.ptr(L), _abi.ptr(R), n, pre, _abi.ptr(out),
                                                        _abi.current_stream(self.device)), "alink_smallres_score_pairs")
+        return out
+
+    def _out(self, out, shape):
+        torch = self.torch
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != tuple(shape) or out.dtype is not torch.float32 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s float32 CUDA tensor" % (tuple(shape),))
+        return out
+
+    def features(self, images, out=None, prescale=None):
+        """The shared tower's output relu(Dense(flatten(tower(image)))) of every image, as an (n, feat) CUDA float32 tensor (`out`,
+        or a new one) — EXTENSION: what the pair head takes, computed once per FACE instead of once per pair occurrence (gallery
+        identification: `score_matrix`, siamese.SmallRes.identify).  Device tensors or arrays, any n, chunked inside the library
+        by 512 images, enqueued on the current stream of the model's device without synchronising.  Under score_pairs' fixed
+        plan (alink_smallres_features): an image has the same BITS alone, in any batch and at any position, and the bits it has
+        inside score_pairs.  prescale as for score_pairs."""
+        x = self._dev(images)
+        n = x.shape[0]
+        if n and tuple(x.shape) != (n, self.H, self.W, 3):
+            raise ValueError("expected an (n, %d, %d, 3) image batch, got %s" % (self.H, self.W, tuple(x.shape)))
+        out = self._out(out, (n, self.feat))
+        pre = self.prescale if prescale is None else (1 if prescale else 0)
+        _abi.check(self.lib.alink_smallres_features(self.h, _abi.ptr(x), n, pre, _abi.ptr(out), _abi.current_stream(self.device)),
+                   "alink_smallres_features")
+        return out
+
+    def score_matrix(self, FL, FR, col=-1, out=None):
+        """scores[i][j] = softmax(head(|FL[i] - FR[j]|)) of two feature matrices (`features`) through the model's own pair head —
+        EXTENSION: an (nL, nR, 2) CUDA float32 tensor, or (nL, nR) holding column `col` alone (col = 0 / 1).  The pairs are
+        enumerated by the kernel, nothing is materialised; element [i][j] has the bits score_pairs gives the pixel pair.  At most
+        2^28 scores (nL * nR * 2) per call: walk a larger matrix in blocks of rows."""
+        FL, FR = self._dev(FL), self._dev(FR)
+        for F in (FL, FR):
+            if F.dim() != 2 or F.shape[1] != self.feat:
+                raise ValueError("expected (n, %d) feature matrices, got %s and %s" % (self.feat, tuple(FL.shape), tuple(FR.shape)))
+        if col not in (-1, 0, 1):
+            raise ValueError("col must be -1 (both columns), 0 or 1, got %r" % (col,))
+        nL, nR = FL.shape[0], FR.shape[0]
+        out = self._out(out, (nL, nR, 2) if col < 0 else (nL, nR))
+        _abi.check(self.lib.alink_smallres_score_features(self.h, _abi.ptr(FL), nL, _abi.ptr(FR), nR, int(col), _abi.ptr(out),
+                                                          _abi.current_stream(self.device)), "alink_smallres_score_features")
         return out
 
     def input_gradients(self, x, y, sample_weight=None, reduction="mean", prescale=None):

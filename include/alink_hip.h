@@ -329,6 +329,20 @@ int alink_committee_forward_multi(alink_head_t* const* heads, int n_heads, const
 int alink_pair_scores_matrix(alink_head_t* const* heads, int n_heads, const float* dev_emb, int n,
                              int row0, int nrows, int col, float* dev_scores, void* stream);
 
+/* The RECTANGULAR score matrix of two feature matrices through one head — what the identification loop of
+ * code/ALINK_MTP.py:279-288 computes one predict() per probe (every probe against every gallery face):
+ *   scores[i][j] = softmax(head(|L[i] - R[j]|)),  i < nL, j < nR
+ * col = -1: both columns, dev_scores is (nL, nR, od); col = 0 .. od - 1: that column alone, dev_scores is (nL, nR).
+ * Pairs are enumerated by the kernel (alink_head_forward's own, row-wise: element [i][j] has the bits
+ * alink_head_forward gives the materialised pair), nothing is materialised; nL == 0 or nR == 0 writes nothing.
+ * LIMIT: nL * nR * od <= ALINK_HEAD_RECT_MAX_SCORES, else ALINK_EINVAL — the kernel's pair and output indices are
+ * 64-bit, but the launch is one workgroup of 256 threads per 32 pairs and a launch holds fewer than 2^32 threads in a
+ * grid dimension (2^29 - 32 pairs); 2^28 scores (1 GiB of float32) stays clear of that for every od.  Walk a larger
+ * matrix in blocks of rows. */
+#define ALINK_HEAD_RECT_MAX_SCORES (1ll << 28)
+int alink_head_forward_rect(alink_head_t* h, const float* dev_L, int nL, const float* dev_R, int nR, int col,
+                            float* dev_scores, void* stream);
+
 /* One Keras train_on_batch: forward, binary_crossentropy (clip 1e-7, mean over the 2 outputs,
  * sample-weighted mean over the batch), backward, [grads left in alink_head_grads_dev],
  * then Adadelta.  dev_y is (n,2) one-hot, dev_sw (n) sample weights or NULL.
@@ -410,6 +424,20 @@ int alink_smallres_forward(alink_smallres_t* m, const float* dev_L, const float*
  * activation buffers are overwritten. */
 int alink_smallres_score_pairs(alink_smallres_t* m, const float* dev_L, const float* dev_R, int n, int prescale,
                                float* dev_probs, void* stream);
+/* EXTENSION (gallery identification: code/ALINK_MTP.py:281-284 re-embeds the probe and the whole gallery for every probe).
+ * The shared tower alone, one image at a time instead of one pair at a time:
+ *   dev_feat[i] = relu(Dense(flatten(tower(dev_images[i]))))          (n, feat) float32, the inputs of the pair head
+ * for ANY n >= 0, chunked inside the call by 512 images, asynchronous on `stream`, under the FIXED PLAN of
+ * alink_smallres_score_pairs.  CONTRACT: a face has the same bits alone, in any batch, in any chunk and at any position, and
+ * the bits it has inside alink_smallres_score_pairs — so alink_smallres_score_features on these rows equals
+ * alink_smallres_score_pairs on the pixel pairs bit for bit.  Parameters, optimizer state and gradient buffers are untouched; the
+ * handle's activation buffers are overwritten. */
+int alink_smallres_features(alink_smallres_t* m, const float* dev_images, int n, int prescale, float* dev_feat, void* stream);
+/* EXTENSION: alink_head_forward_rect through the model's OWN pair head (code/ALINK_MTP.py:284's predict on features computed
+ * once): scores[i][j] = softmax(head(|L[i] - R[j]|)) of two feature matrices (nL, feat) and (nR, feat); col, the shape of
+ * dev_scores and the size limit as there. */
+int alink_smallres_score_features(alink_smallres_t* m, const float* dev_L, int nL, const float* dev_R, int nR, int col,
+                                  float* dev_scores, void* stream);
 /* one Keras train_on_batch (apply != 0) or gradients only.  dev_masks: the two dropout keep-masks for
  * the 2n tower passes, u8, laid out [2n*P1*P1*32] then [2n*P2*P2*64] (1 = keep), or NULL = no dropout.
  * dev_metrics: {loss, binary_accuracy}. */
@@ -467,6 +495,19 @@ int alink_score(int kind, const float* dev_probs, const float* dev_b, int col, i
 size_t alink_topk_scratch_bytes(int64_t P, int k);
 int alink_topk(const float* dev_scores, int64_t P, int k, int largest, int32_t* dev_idx,
                float* dev_vals, void* dev_scratch, void* stream);
+/* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
+ * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
+ * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):
+ *   dev_flat_argmax[p] = np.argmax of row p FLATTENED to G * C: the first maximum.  This is the index the reference compares
+ *                        with the person id (its quirk: gallery g wins through column c at index g * C + c).
+ *   dev_best[p]        = the lowest g that maximises scores[p][g][col]                                     (EXTENSION)
+ *   dev_rank[p]        = the 0-based position of gallery dev_true[p] in a STABLE descending sort of column col: the number
+ *                        of g with a strictly larger score plus the number of g < dev_true[p] with an equal one; -1 when
+ *                        dev_true[p] is outside 0 .. G - 1 (the row is not read at that index).  Needs dev_true.  (EXTENSION)
+ * Comparisons are `>`: a NaN never wins (np.argmax would return it) and counts as neither larger nor equal.
+ * 0 <= col < C, G >= 1, G * C < 2^31; P == 0 writes nothing. */
+int alink_identify_rows(const float* dev_scores, int P, int G, int C, int col, const int32_t* dev_true,
+                        int32_t* dev_flat_argmax, int32_t* dev_best, int32_t* dev_rank, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DFW protocol evaluation (utilities/ROC_precompute.py:19-63): over the strict upper triangle of an

@@ -57,6 +57,9 @@ PROTOTYPES = {
     "alink_embed_input_grad": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "alink_embed_profile": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
     "alink_conv_nhwc": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    "alink_conv_nhwc_ex": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_i, _vp, _i, _vp, _vp, _i, _i, _i]
+                           + [C.POINTER(_i), C.POINTER(_i), _vp]),
+    "alink_conv_nhwc_x2_ex": (_i, [_vp] * 6 + [_i] * 14 + [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "alink_resnet50_create": (_vp, [_i, _i, _i, _f]),
     "alink_resnet50_destroy": (None, [_vp]),
     "alink_resnet50_num_tensors": (_i, [_vp]),

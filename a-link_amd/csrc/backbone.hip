@@ -1342,58 +1342,158 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
     return ALINK_OK;
 }
 
-// ---- diagnostic single-convolution entry (unit tests) -------------------------------------------
-int alink_conv_nhwc(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
-                    const float* dev_alpha, const void* dev_resid, void* dev_out, int N, int H, int W, int Cin,
-                    int Cout, int ksz, int stride, int pad, int border_cls, int fine, void* stream) {
+// ---- diagnostic single-convolution entries (unit tests) -----------------------------------------
+// What alink_conv_nhwc_ex / alink_conv_nhwc_x2_ex add to the plain entries (the defaults are the plain entries' launch).
+struct ConvExtras {
+    int route = 0;                // 0: direct_variant, 1: direct_variant_tiles (16-bit; split precision has one chooser)
+    const void* dact = nullptr;   // backward epilogue: the stored forward activation
+    int post_relu = 0;
+    const void* in2 = nullptr;    // fused 1x1 projection shortcut: its operand, its natural [Cout][Cin2] weights
+    const void* w2 = nullptr;
+    int Cin2 = 0, in2_compact = 0;
+    int splitk = 1;               // > 1: f32 slabs + launch_conv_split_finish
+    int nprod = 0;                // split precision: 3 (0 = 3) or 1
+    int* kernel = nullptr;        // out: the ConvKernel chosen
+    int* form = nullptr;          // out: 0 = that kernel, 1 = conv3x3_lat_kernel, 2 = conv_gemm_lat_kernel
+};
+
+// Which kernel serves launch_conv(k, dtype, q): the launchers' own hand-off predicates on the ConvParams that is launched.
+static int served_form(ConvKernel k, int dtype, const ConvParams& q) {
+    if (k == ConvKernel::Igemm) return conv_gemm_lat_applies(dtype, q) ? 2 : 0;          // launch_conv_igemm
+    if (traits(k).channel_block) return conv3x3_lat_applies(dtype, q) ? 1 : 0;           // launch_conv3x3_linear
+    return 0;
+}
+
+// Requests the entries turn down before anything is allocated: what a launcher would refuse, and what one would ignore.
+static int check_extras(ConvKernel kernel, int dtype, int ksz, int Cin, const float* dev_alpha, const void* dev_resid,
+                        const ConvExtras& x) {
+    const bool x2 = dtype == ALINK_DT_F16X2;
+    const bool rolling = kernel == ConvKernel::Roll112 || kernel == ConvKernel::Roll112S2;
+    ALINK_REQUIRE(x.splitk >= 1 && x.splitk <= 8, ALINK_EINVAL, "splitk must be 1..8");
+    ALINK_REQUIRE(x.nprod == 0 || x.nprod == 1 || x.nprod == 3, ALINK_EINVAL, "nprod must be 3 or 1");
+    ALINK_REQUIRE(!x.dact || !x2, ALINK_EINVAL, "split precision has no backward epilogue (dact)");
+    ALINK_REQUIRE(!x.dact || (dev_alpha && !dev_resid), ALINK_EINVAL, "the backward epilogue (dact) needs the PReLU slopes and takes no residual");
+    ALINK_REQUIRE(!rolling || (!x.dact && !x.post_relu && x.splitk == 1), ALINK_EINVAL,
+                  "the rolling-row kernels have forward epilogues only (no dact, post_relu or K split)");
+    if (x.in2) {
+        ALINK_REQUIRE(!x2, ALINK_EINVAL, "split precision has no fused shortcut");
+        ALINK_REQUIRE(x.w2 && x.Cin2 > 0 && x.Cin2 % 64 == 0, ALINK_EINVAL, "fused shortcut: needs dev_w2 and Cin2 a multiple of 64");
+        ALINK_REQUIRE(kernel == ConvKernel::Igemm || kernel == ConvKernel::Roll112S2, ALINK_EINVAL,
+                      "fused shortcut: kernel %d has no shortcut form", (int)kernel);
+        ALINK_REQUIRE(x.splitk == 1 && !x.dact, ALINK_EINVAL, "fused shortcut: one fused forward launch only (no K split, no dact)");
+        ALINK_REQUIRE(kernel != ConvKernel::Roll112S2 || (x.Cin2 == 64 && !dev_alpha && !dev_resid), ALINK_EINVAL,
+                      "conv3x3_s2c64's shortcut form: Cin2 = 64, no PReLU, no residual");
+    } else {
+        ALINK_REQUIRE(!x.w2 && x.Cin2 == 0, ALINK_EINVAL, "dev_w2 / Cin2 without dev_in2");
+    }
+    if (x.splitk > 1) {
+        const SplitUnit u = traits(kernel).split;
+        ALINK_REQUIRE(u != SplitUnit::None, ALINK_EINVAL, "kernel %d has no K-split form", (int)kernel);
+        const int units = u == SplitUnit::Chunk ? Cin / 64 : ksz * ksz * (Cin / 64);
+        ALINK_REQUIRE(units % x.splitk == 0, ALINK_EINVAL, "splitk %d does not divide the %d %s", x.splitk, units,
+                      u == SplitUnit::Chunk ? "input chunks" : "K-steps");
+    }
+    return ALINK_OK;
+}
+
+// the launch itself: fused, or S slabs of f32 partial sums and their finish (divided as alink_embed divides)
+static hipError_t launch_conv_maybe_split(ConvKernel kernel, int dtype, const ConvParams& p, int S, float* slabs,
+                                          const ConvExtras& x, hipStream_t st) {
+    ConvParams q = p;
+    if (S > 1) { q.out = slabs; q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S; }
+    if (x.kernel) *x.kernel = (int)kernel;
+    if (x.form) *x.form = served_form(kernel, dtype, q);
+    hipError_t e = launch_conv(kernel, dtype, q, st);
+    if (e == hipSuccess && S > 1) e = launch_conv_split_finish(dtype, p, slabs, S, st);
+    return e;
+}
+
+static int conv_nhwc_impl(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
+                          const float* dev_alpha, const void* dev_resid, void* dev_out, int N, int H, int W, int Cin,
+                          int Cout, int ksz, int stride, int pad, int border_cls, int fine, const ConvExtras& x, void* stream) {
     ALINK_REQUIRE(dev_in && dev_w && dev_bias && dev_out, ALINK_EINVAL, "NULL argument");
     DeviceGuard dg(device_of_pointer(dev_in));
     ALINK_REQUIRE(Cin % 64 == 0 && Cout % 64 == 0, ALINK_EINVAL, "Cin/Cout must be multiples of 64");
     ALINK_REQUIRE(ksz == 1 || ksz == 3, ALINK_EINVAL, "ksz must be 1 or 3");
     ALINK_REQUIRE(!border_cls || (ksz == 3 && stride == 1 && pad == 1), ALINK_EINVAL,
                   "border classes need a 3x3 stride-1 pad-1 convolution");
+    ALINK_REQUIRE(dtype == ALINK_DT_BF16 || dtype == ALINK_DT_F16, ALINK_EINVAL, "dtype must be bf16 or f16");
     int rc = init_kernels();
     if (rc) return rc;
+    const ConvKernel kernel = x.route ? direct_variant_tiles(ksz, stride, pad, H, W, Cin, Cout)
+                                      : direct_variant(ksz, stride, pad, H, W, Cin, Cout);
+    if ((rc = check_extras(kernel, dtype, ksz, Cin, dev_alpha, dev_resid, x))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int K = ksz * ksz * Cin;
-    // permute weight rows into a private copy
-    std::vector<uint16_t> h((size_t)Cout * K), hp((size_t)Cout * K);
+    const int K = ksz * ksz * Cin, Cin2 = x.in2 ? x.Cin2 : 0;
+    // permute weight rows into a private copy (the shortcut's columns behind the taps of the same row)
+    const WeightLayout wl = weight_layout(kernel, ksz, Cin, false, Cin2);
+    std::vector<uint16_t> h((size_t)Cout * K), h2((size_t)Cout * Cin2), hp(wl.size(Cout));
     ALINK_HIP(hipStreamSynchronize(st));
     ALINK_HIP(hipMemcpy(h.data(), dev_w, h.size() * 2, hipMemcpyDeviceToHost));
-    const ConvKernel kernel = direct_variant(ksz, stride, pad, H, W, Cin, Cout);
-    const WeightLayout wl = weight_layout(kernel, ksz, Cin);
-    for (int co = 0; co < Cout; ++co)
+    if (Cin2) ALINK_HIP(hipMemcpy(h2.data(), x.w2, h2.size() * 2, hipMemcpyDeviceToHost));
+    for (int co = 0; co < Cout; ++co) {
         for (int tap = 0; tap < ksz * ksz; ++tap)
             for (int ci = 0; ci < Cin; ++ci) hp[wl.at(co, tap, ci)] = h[(size_t)co * K + (size_t)tap * Cin + ci];
-    void *d_wp = nullptr, *d_zero = nullptr;
-    ALINK_HIP(hipMalloc(&d_wp, hp.size() * 2));
-    ALINK_HIP(hipMalloc(&d_zero, 4096));
-    ALINK_HIP(hipMemcpy(d_wp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
-    ALINK_HIP(hipMemset(d_zero, 0, 4096));
+        for (int ci = 0; ci < Cin2; ++ci) hp[wl.at_shortcut(co, ci)] = h2[(size_t)co * Cin2 + ci];
+    }
     ConvParams p{};
-    p.in = dev_in; p.wgt = d_wp; p.bias = dev_bias; p.alpha = dev_alpha; p.resid = dev_resid; p.out = dev_out;
-    p.zero = d_zero; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+    p.in = dev_in; p.bias = dev_bias; p.alpha = dev_alpha; p.resid = dev_resid; p.dact = x.dact; p.out = dev_out;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
     p.Ho = conv_out(H, ksz, stride, pad); p.Wo = conv_out(W, ksz, stride, pad);
     p.stride = stride; p.ksz = ksz; p.pad = pad; p.M = N * p.Ho * p.Wo; p.border_cls = border_cls;
-    p.splitk = 1; p.ksteps_per_split = ksz * ksz * (Cin / 64);
+    p.splitk = 1; p.ksteps_per_split = ksz * ksz * (Cin / 64) + Cin2 / 64;
+    p.post_relu = x.post_relu;
+    if (Cin2) { p.in2 = x.in2; p.Cin2 = Cin2; p.in2_compact = x.in2_compact ? 1 : 0; }
     p.ablate = g_ablate; p.stamps = g_stamps;
     // fine: 1 / 0 force the 64- / 128-channel form of the linear-tile kernel, < 0 chooses as alink_embed does
     if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
-    hipError_t e = launch_conv(kernel, dtype, p, st);
+    void *d_wp = nullptr, *d_zero = nullptr, *d_slabs = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_wp); (void)hipFree(d_zero); (void)hipFree(d_slabs); };
+#define EX_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call, __FILE__, __LINE__); } } while (0)
+    EX_TRY(hipMalloc(&d_wp, hp.size() * 2));
+    EX_TRY(hipMalloc(&d_zero, 4096));
+    if (x.splitk > 1) EX_TRY(hipMalloc(&d_slabs, (size_t)x.splitk * p.M * Cout * 4));
+    EX_TRY(hipMemcpy(d_wp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
+    EX_TRY(hipMemset(d_zero, 0, 4096));
+    p.wgt = d_wp; p.zero = d_zero;
+    hipError_t e = launch_conv_maybe_split(kernel, dtype, p, x.splitk, (float*)d_slabs, x, st);
     hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(d_wp);
-    (void)hipFree(d_zero);
-    if (e != hipSuccess) return hip_fail(e, "launch_conv_igemm", __FILE__, __LINE__);
+#undef EX_TRY
+    cleanup();
+    if (e != hipSuccess) return hip_fail(e, "launch_conv", __FILE__, __LINE__);
     if (e2 != hipSuccess) return hip_fail(e2, "hipStreamSynchronize", __FILE__, __LINE__);
     return ALINK_OK;
+}
+
+int alink_conv_nhwc(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
+                    const float* dev_alpha, const void* dev_resid, void* dev_out, int N, int H, int W, int Cin,
+                    int Cout, int ksz, int stride, int pad, int border_cls, int fine, void* stream) {
+    return conv_nhwc_impl(dtype, dev_in, dev_w, dev_bias, dev_alpha, dev_resid, dev_out, N, H, W, Cin, Cout, ksz, stride, pad,
+                          border_cls, fine, ConvExtras{}, stream);
+}
+
+int alink_conv_nhwc_ex(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
+                       const float* dev_alpha, const void* dev_resid, void* dev_out, int N, int H, int W, int Cin,
+                       int Cout, int ksz, int stride, int pad, int border_cls, int fine, int route, const void* dev_dact,
+                       int post_relu, const void* dev_in2, const void* dev_w2, int Cin2, int in2_compact, int splitk,
+                       int* kernel_out, int* form_out, void* stream) {
+    ConvExtras x;
+    x.route = route ? 1 : 0; x.dact = dev_dact; x.post_relu = post_relu ? 1 : 0;
+    x.in2 = dev_in2; x.w2 = dev_w2; x.Cin2 = Cin2; x.in2_compact = in2_compact; x.splitk = splitk;
+    x.kernel = kernel_out; x.form = form_out;
+    if (kernel_out) *kernel_out = -1;
+    if (form_out) *form_out = -1;
+    return conv_nhwc_impl(dtype, dev_in, dev_w, dev_bias, dev_alpha, dev_resid, dev_out, N, H, W, Cin, Cout, ksz, stride, pad,
+                          border_cls, fine, x, stream);
 }
 
 
 // Split-precision twin of alink_conv_nhwc (unit tests): float32 tensors in natural layouts on the device, converted
 // to / from the f16-pair layouts on the HOST (synchronous, test use only).  Stored value = true value x 2^e.
-int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev_bias, const float* dev_alpha,
-                       const float* dev_resid, float* dev_out, int N, int H, int W, int Cin, int Cout, int ksz, int stride,
-                       int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res, void* stream) {
+static int conv_nhwc_x2_impl(const float* dev_in, const float* dev_w, const float* dev_bias, const float* dev_alpha,
+                             const float* dev_resid, float* dev_out, int N, int H, int W, int Cin, int Cout, int ksz, int stride,
+                             int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res, const ConvExtras& x,
+                             void* stream) {
     ALINK_REQUIRE(dev_in && dev_w && dev_bias && dev_out, ALINK_EINVAL, "NULL argument");
     DeviceGuard dg(device_of_pointer(dev_in));
     ALINK_REQUIRE(Cin % 64 == 0 && Cout % 64 == 0, ALINK_EINVAL, "Cin/Cout must be multiples of 64");
@@ -1403,10 +1503,11 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
     int rc = init_kernels();
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    const ConvKernel kernel = linear_variant_x2(ksz, stride, pad, H, W, Cin, Cout);
+    if ((rc = check_extras(kernel, ALINK_DT_F16X2, ksz, Cin, dev_alpha, dev_resid, x))) return rc;
     ALINK_HIP(hipStreamSynchronize(st));
     const int K = ksz * ksz * Cin, Ho = conv_out(H, ksz, stride, pad), Wo = conv_out(W, ksz, stride, pad);
     const size_t Min = (size_t)N * H * W, M = (size_t)N * Ho * Wo;
-    const ConvKernel kernel = linear_variant_x2(ksz, stride, pad, H, W, Cin, Cout);
     const WeightLayout wl = weight_layout(kernel, ksz, Cin, true);
     auto pack_act = [&](const float* dev, size_t rows, int C, int e, std::vector<uint16_t>& q) -> int {
         std::vector<float> h(rows * C);
@@ -1432,13 +1533,14 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
                     split16(std::ldexp((double)h[(size_t)co * K + (size_t)tap * Cin + ci], e_w), &qw[at], &qw[at + wl.lo_offset()]);
                 }
     }
-    void *d_in = nullptr, *d_res = nullptr, *d_w = nullptr, *d_out = nullptr, *d_zero = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_in); (void)hipFree(d_res); (void)hipFree(d_w); (void)hipFree(d_out); (void)hipFree(d_zero); };
+    void *d_in = nullptr, *d_res = nullptr, *d_w = nullptr, *d_out = nullptr, *d_zero = nullptr, *d_slabs = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_in); (void)hipFree(d_res); (void)hipFree(d_w); (void)hipFree(d_out); (void)hipFree(d_zero); (void)hipFree(d_slabs); };
 #define X2_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call, __FILE__, __LINE__); } } while (0)
     X2_TRY(hipMalloc(&d_in, qin.size() * 2));
     X2_TRY(hipMalloc(&d_w, qw.size() * 2));
     X2_TRY(hipMalloc(&d_out, M * Cout * 4));
     X2_TRY(hipMalloc(&d_zero, 4096));
+    if (x.splitk > 1) X2_TRY(hipMalloc(&d_slabs, (size_t)x.splitk * M * Cout * 4));
     X2_TRY(hipMemcpy(d_in, qin.data(), qin.size() * 2, hipMemcpyHostToDevice));
     X2_TRY(hipMemcpy(d_w, qw.data(), qw.size() * 2, hipMemcpyHostToDevice));
     X2_TRY(hipMemset(d_zero, 0, 4096));
@@ -1451,11 +1553,12 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
     p.zero = d_zero; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
     p.stride = stride; p.ksz = ksz; p.pad = pad; p.M = (int)M; p.border_cls = border_cls;
     p.splitk = 1; p.ksteps_per_split = 3 * ksz * ksz * (Cin / 64);
+    p.post_relu = x.post_relu; p.nprod = x.nprod;
     p.acc_scale = std::ldexp(1.f, e_out - e_in - e_w);
     p.bias_scale = std::ldexp(1.f, e_out);
     p.res_scale = std::ldexp(1.f, e_out - e_res);
     if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
-    X2_TRY(launch_conv(kernel, ALINK_DT_F16X2, p, st));
+    X2_TRY(launch_conv_maybe_split(kernel, ALINK_DT_F16X2, p, x.splitk, (float*)d_slabs, x, st));
     X2_TRY(hipStreamSynchronize(st));
     std::vector<uint16_t> qo(M * Cout * 2);
     X2_TRY(hipMemcpy(qo.data(), d_out, qo.size() * 2, hipMemcpyDeviceToHost));
@@ -1472,6 +1575,25 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
 #undef X2_TRY
     cleanup();
     return ALINK_OK;
+}
+
+int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev_bias, const float* dev_alpha,
+                       const float* dev_resid, float* dev_out, int N, int H, int W, int Cin, int Cout, int ksz, int stride,
+                       int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res, void* stream) {
+    return conv_nhwc_x2_impl(dev_in, dev_w, dev_bias, dev_alpha, dev_resid, dev_out, N, H, W, Cin, Cout, ksz, stride, pad, border_cls,
+                             fine, e_in, e_w, e_out, e_res, ConvExtras{}, stream);
+}
+
+int alink_conv_nhwc_x2_ex(const float* dev_in, const float* dev_w, const float* dev_bias, const float* dev_alpha,
+                          const float* dev_resid, float* dev_out, int N, int H, int W, int Cin, int Cout, int ksz, int stride,
+                          int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res, int nprod, int splitk,
+                          int post_relu, int* kernel_out, int* form_out, void* stream) {
+    ConvExtras x;
+    x.nprod = nprod; x.splitk = splitk; x.post_relu = post_relu ? 1 : 0; x.kernel = kernel_out; x.form = form_out;
+    if (kernel_out) *kernel_out = -1;
+    if (form_out) *form_out = -1;
+    return conv_nhwc_x2_impl(dev_in, dev_w, dev_bias, dev_alpha, dev_resid, dev_out, N, H, W, Cin, Cout, ksz, stride, pad, border_cls,
+                             fine, e_in, e_w, e_out, e_res, x, stream);
 }
 
 }  // extern "C"

@@ -191,6 +191,30 @@ int alink_conv_nhwc_x2(const float* dev_in, const float* dev_w, const float* dev
                        int stride, int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res,
                        void* stream);
 
+/* Diagnostic / unit-test entries that reach every launch form and report what ran.  alink_conv_nhwc_ex is alink_conv_nhwc plus:
+ *   route        0 = the kernel direct_variant chooses (the 16-bit forward), 1 = direct_variant_tiles (backward passes, ResNet-50, VGG16)
+ *   dev_dact     (M, Cout) in `dtype`, or NULL: backward epilogue, out = (conv + bias) * (dact > 0 ? 1 : alpha[c]); needs dev_alpha
+ *   post_relu    ReLU after the residual add (keeps a NaN)
+ *   dev_in2, dev_w2, Cin2, in2_compact: a fused 1x1 projection shortcut, out += conv1x1(in2, w2) sampled at (oy * stride, ox * stride);
+ *                dev_in2 (N, H, W, Cin2), or (N, Ho, Wo, Cin2) if in2_compact; dev_w2 (Cout, Cin2) in natural order
+ *   splitk       > 1: the K walk cut into that many f32 slabs (allocated by the call) and summed by the split-finish kernel
+ *   kernel_out   the ConvKernel value chosen (csrc/conv_kernel.h), form_out: 0 = that kernel itself, 1 = conv3x3_lat_kernel,
+ *                2 = conv_gemm_lat_kernel; either may be NULL; both are -1 when the call fails before choosing
+ * A combination the chosen kernel has no form of (the rolling-row kernels with dact / post_relu / splitk, a shortcut on a tile
+ * kernel, split precision with dact ...) returns an error code with alink_last_error set and launches nothing. */
+int alink_conv_nhwc_ex(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
+                       const float* dev_alpha, const void* dev_resid, void* dev_out,
+                       int N, int H, int W, int Cin, int Cout, int ksz, int stride, int pad,
+                       int border_cls, int fine, int route, const void* dev_dact, int post_relu,
+                       const void* dev_in2, const void* dev_w2, int Cin2, int in2_compact, int splitk,
+                       int* kernel_out, int* form_out, void* stream);
+
+/* alink_conv_nhwc_x2 plus nprod (3, or 1: the one-product screening form), splitk, post_relu and the two reports. */
+int alink_conv_nhwc_x2_ex(const float* dev_in, const float* dev_w, const float* dev_bias, const float* dev_alpha,
+                          const float* dev_resid, float* dev_out, int N, int H, int W, int Cin, int Cout, int ksz,
+                          int stride, int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res,
+                          int nprod, int splitk, int post_relu, int* kernel_out, int* form_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * VGGFace2 ResNet-50 feature extractor: siamese.RESNET50 (code/siamese.py:203-216) =
  * keras_vggface VGGFace(model='resnet50', include_top=False) cut at 'avg_pool', flattened (2048-d),

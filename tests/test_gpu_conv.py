@@ -9,33 +9,55 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+# ConvKernel values (a-link_amd/csrc/conv_kernel.h) and launch forms alink_conv_nhwc_ex reports
+IGEMM, D4, D5, S1, S3, LIN14, LIN28, LIN56, LIN7, ROLL112, ROLL112S2 = 0, 4, 5, 7, 8, 11, 12, 13, 14, 21, 25
+SELF, LAT3X3, LATGEMM = 0, 1, 2      # the kernel itself, conv3x3_lat_kernel, conv_gemm_lat_kernel
+
+# Each case: the shape and epilogue, then what serves it (kernel, form) in the library's default setting and with the
+# linear-tile kernel off (alink_debug_set_linear(0)) — asserted against alink_conv_nhwc_ex's report.  The row-aligned tile
+# kernels TileW14C256 / TileW28C256 / TileW28C128 never appear: the pair kernels take every Cout % 128 == 0 first
+# (tests/test_gpu_conv_forms.py reaches them with alink_debug_set_pair(0)).
 CASES = [
     # N, H, W, Cin, Cout, ksz, stride, pad, border, alpha, resid
-    (2, 14, 14, 64, 64, 3, 1, 1, 1, 1, 0),      # unit conv1: border classes + PReLU, 256x64 tile
-    (2, 14, 14, 64, 64, 3, 2, 1, 0, 0, 1),      # unit conv2 stride 2 + residual
-    (1, 12, 10, 128, 128, 3, 1, 1, 1, 1, 0),    # 128x128 tile, ragged M (120 pixels)
-    (3, 8, 8, 64, 128, 1, 2, 0, 0, 0, 0),       # 1x1 stride-2 shortcut
-    (2, 7, 7, 256, 256, 3, 1, 1, 0, 0, 1),      # stage-4 like, K = 2304
-    (1, 9, 9, 128, 64, 3, 2, 1, 0, 0, 0),       # odd size, stride 2
-    (5, 16, 16, 64, 192, 3, 1, 1, 1, 1, 1),     # Cout not a multiple of 128 -> 256x64 tile path
-    # shapes served by conv3x3_direct.hip (input tile resident in LDS), one per variant D1..D6
-    (3, 14, 14, 256, 256, 3, 1, 1, 1, 1, 0),    # D1: stage-3 conv1 (border classes + PReLU)
-    (2, 14, 14, 128, 512, 3, 1, 1, 0, 0, 1),    # D1: two channel tiles, residual, Cin = 2 chunks
-    (2, 28, 28, 128, 256, 3, 1, 1, 1, 1, 0),    # D2
-    (2, 28, 28, 128, 128, 3, 1, 1, 0, 0, 1),    # D3: stage-2 conv2-like
-    (1, 28, 28, 64, 128, 3, 1, 1, 1, 1, 1),     # D3 with a single input chunk
-    (2, 56, 56, 64, 128, 3, 1, 1, 1, 1, 0),     # D4
-    (2, 56, 56, 64, 64, 3, 1, 1, 1, 1, 1),      # D5: stage 1
-    (1, 112, 112, 64, 64, 3, 1, 1, 1, 1, 0),    # stage-1 unit-1 conv1: the rolling-row kernel (conv3x3_c64.hip; D6 with linear = 0)
+    (2, 14, 14, 64, 64, 3, 1, 1, 1, 1, 0),      # conv_igemm, 256x64 tile (Cout = 64: no tile kernel at 14 wide): border classes + PReLU
+    (2, 14, 14, 64, 64, 3, 2, 1, 0, 0, 1),      # unit conv2 stride 2 + residual: conv_gemm_lat_kernel (98 pixels)
+    (1, 12, 10, 128, 128, 3, 1, 1, 1, 1, 0),    # conv_igemm, 128x128 tile, ragged M (120 pixels)
+    (3, 8, 8, 64, 128, 1, 2, 0, 0, 0, 0),       # 1x1 stride-2 shortcut: conv_gemm_lat_kernel
+    (2, 7, 7, 256, 256, 3, 1, 1, 0, 0, 1),      # stage-4 like, K = 2304: conv3x3_lat_kernel; conv_igemm with linear = 0
+    (1, 9, 9, 128, 64, 3, 2, 1, 0, 0, 0),       # odd size, stride 2: conv_gemm_lat_kernel
+    (5, 16, 16, 64, 192, 3, 1, 1, 1, 1, 1),     # conv_igemm: Cout not a multiple of 128 -> 256x64 tile path
+    # stride-1 3x3 layers: the linear-tile kernel or its latency form; with linear = 0 the pair kernels (PairW14C128,
+    # PairW28C128) and the 56-wide row-aligned tile kernels of conv3x3_direct.hip
+    (3, 14, 14, 256, 256, 3, 1, 1, 1, 1, 0),    # stage-3 conv1 (border classes + PReLU): latency form | PairW14C128
+    (2, 14, 14, 128, 512, 3, 1, 1, 0, 0, 1),    # four channel tiles, residual, Cin = 2 chunks: latency form | PairW14C128
+    (2, 28, 28, 128, 256, 3, 1, 1, 1, 1, 0),    # latency form (1568 pixels, 392 waves) | PairW28C128
+    (2, 28, 28, 128, 128, 3, 1, 1, 0, 0, 1),    # stage-2 conv2-like: latency form | PairW28C128
+    (1, 28, 28, 64, 128, 3, 1, 1, 1, 1, 1),     # a single input chunk: Linear28 itself | PairW28C128
+    (2, 56, 56, 64, 128, 3, 1, 1, 1, 1, 0),     # Linear56 | TileW56C128
+    (2, 56, 56, 64, 64, 3, 1, 1, 1, 1, 1),      # stage 1: Linear56 | TileW56C64
+    (1, 112, 112, 64, 64, 3, 1, 1, 1, 1, 0),    # stage-1 unit-1 conv1: the rolling-row kernel (conv3x3_c64.hip), whatever the linear switch
     (3, 112, 112, 64, 64, 3, 1, 1, 0, 0, 1),    # the same kernel: three images (bands of several images per workgroup), residual
     (37, 112, 112, 64, 64, 3, 1, 1, 1, 1, 1),   # 259 bands for 256 persistent workgroups: some take two; PReLU + residual
     (41, 28, 28, 128, 128, 3, 1, 1, 0, 0, 1),   # stage-2 conv2 over 41 images: 144 groups of 224 pixels, most of them across image boundaries
     (21, 56, 56, 64, 64, 3, 1, 1, 1, 1, 0),     # stage-1 unit over 21 images: 294 groups of 224 pixels across image boundaries
     (3, 112, 112, 64, 64, 3, 2, 1, 0, 0, 1),    # the direct stride-2 kernel (conv3x3_s2c64.hip), plain form: residual; one output row per pass
     (9, 112, 112, 64, 64, 3, 2, 1, 0, 1, 0),    # the same: 504 output rows for 256 workgroups (runs of 1-2 rows across images), PReLU
-    (2, 13, 14, 64, 256, 3, 1, 1, 1, 0, 0),     # D1 with a ragged row count (H not a multiple of R)
-    (1, 30, 28, 64, 128, 3, 1, 1, 0, 1, 0),     # D3 ragged rows
+    (2, 13, 14, 64, 256, 3, 1, 1, 1, 0, 0),     # PairW14C128 with a ragged row count (H not a multiple of R; not square: no linear tiles)
+    (1, 30, 28, 64, 128, 3, 1, 1, 0, 1, 0),     # PairW28C128, ragged rows
 ]
+# (kernel, form) per case of CASES: library default, then with alink_debug_set_linear(0)
+SERVED = [
+    ((IGEMM, SELF), (IGEMM, SELF)), ((IGEMM, LATGEMM), (IGEMM, LATGEMM)), ((IGEMM, SELF), (IGEMM, SELF)),
+    ((IGEMM, LATGEMM), (IGEMM, LATGEMM)), ((LIN7, LAT3X3), (IGEMM, SELF)), ((IGEMM, LATGEMM), (IGEMM, LATGEMM)),
+    ((IGEMM, SELF), (IGEMM, SELF)),
+    ((LIN14, LAT3X3), (S1, SELF)), ((LIN14, LAT3X3), (S1, SELF)), ((LIN28, LAT3X3), (S3, SELF)), ((LIN28, LAT3X3), (S3, SELF)),
+    ((LIN28, SELF), (S3, SELF)), ((LIN56, SELF), (D4, SELF)), ((LIN56, SELF), (D5, SELF)),
+    ((ROLL112, SELF), (ROLL112, SELF)), ((ROLL112, SELF), (ROLL112, SELF)), ((ROLL112, SELF), (ROLL112, SELF)),
+    ((LIN28, SELF), (S3, SELF)), ((LIN56, SELF), (D5, SELF)),
+    ((ROLL112S2, SELF), (ROLL112S2, SELF)), ((ROLL112S2, SELF), (ROLL112S2, SELF)),
+    ((S1, SELF), (S1, SELF)), ((S3, SELF), (S3, SELF)),
+]
+assert len(SERVED) == len(CASES)
 
 
 def _ref(x, w, bias, alpha, resid, stride, pad, border):
@@ -61,8 +83,11 @@ LINEAR_CASES = [
     (11, 14, 14, 128, 256, 3, 1, 1, 1, 1, 1),   # 11 images: groups straddle image boundaries, ragged tail
     (3, 28, 28, 64, 128, 3, 1, 1, 1, 0, 1),
     (1, 56, 56, 64, 64, 3, 1, 1, 0, 1, 0),
-    (9, 7, 7, 128, 128, 3, 1, 1, 1, 1, 1),      # 16-pixel tiles span three rows; 4.6 images per group
+    (9, 7, 7, 128, 128, 3, 1, 1, 1, 1, 1),      # 16-pixel tiles span three rows; 4.6 images per group: 441 pixels, so the latency
+                                                # form serves it (the linear-tile kernel proper: tests/test_gpu_conv_forms.py)
 ]
+LINEAR_SERVED = [((LIN14, SELF), (S1, SELF)), ((LIN28, SELF), (S3, SELF)), ((LIN56, SELF), (D5, SELF)), ((LIN7, LAT3X3), (IGEMM, SELF))]
+assert len(LINEAR_SERVED) == len(LINEAR_CASES)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -76,7 +101,7 @@ def test_conv_matches_cpu(gpu, dt, dma, linear):
     code = gpu.DT_BF16 if dt == "bf16" else gpu.DT_F16
     g = torch.Generator().manual_seed(1234)
     try:
-        for (N, H, W, Ci, Co, k, s, p, border, use_alpha, use_resid) in CASES + LINEAR_CASES:
+        for (N, H, W, Ci, Co, k, s, p, border, use_alpha, use_resid), served in zip(CASES + LINEAR_CASES, SERVED + LINEAR_SERVED):
             x = (torch.randn(N, H, W, Ci, generator=g)).to(tdt)
             w = (torch.randn(Co, k, k, Ci, generator=g) * (1.0 / np.sqrt(k * k * Ci))).to(tdt)
             ncls = 9 if border else 1
@@ -92,9 +117,14 @@ def test_conv_matches_cpu(gpu, dt, dma, linear):
             is_linear_case = (N, H, W, Ci, Co, k, s, p, border, use_alpha, use_resid) in LINEAR_CASES
             for fine in ((0, 1) if is_linear_case else (-1,)):      # both forms of the linear-tile kernel
                 out.fill_(float("nan"))
-                rc = lib.alink_conv_nhwc(code, gpu.ptr(xd), gpu.ptr(wd), gpu.ptr(bd), gpu.ptr(ad), gpu.ptr(rd),
-                                         gpu.ptr(out), N, H, W, Ci, Co, k, s, p, border, fine, None)
-                gpu.check(rc, "alink_conv_nhwc")
+                kern, form = C.c_int(-1), C.c_int(-1)
+                rc = lib.alink_conv_nhwc_ex(code, gpu.ptr(xd), gpu.ptr(wd), gpu.ptr(bd), gpu.ptr(ad), gpu.ptr(rd),
+                                            gpu.ptr(out), N, H, W, Ci, Co, k, s, p, border, fine,
+                                            0, None, 0, None, None, 0, 0, 1, C.byref(kern), C.byref(form), None)
+                gpu.check(rc, "alink_conv_nhwc_ex")
+                # the kernel and form this case is written for: it cannot silently run something else
+                assert (kern.value, form.value) == served[0 if linear < 0 else 1], (
+                    (N, H, W, Ci, Co, k, s, p), linear, kern.value, form.value)
                 _check_conv(out, ref, dt, (N, H, W, Ci, Co, k, s, p, border, fine), dma)
     finally:
         lib.alink_debug_set_dma(1)
@@ -191,6 +221,7 @@ def test_linear_kernel_fuzz(gpu):
     lib = gpu.load()
     rng = np.random.RandomState(2024)
     g = torch.Generator().manual_seed(99)
+    n_lat = 0
     for case in range(24):
         W = [7, 14, 28, 56][case % 4]
         N = int(rng.randint(1, {7: 40, 14: 24, 28: 7, 56: 3}[W] + 1))
@@ -209,17 +240,36 @@ def test_linear_kernel_fuzz(gpu):
         rd = resid.cuda() if use_resid else None
         # both workgroup forms of the kernel (128- and 64-channel; the 56-wide variant has one form): each against
         # the CPU reference, and against each other BIT FOR BIT — alink_embed switches between them by batch size
-        # (ConvParams::fine) and promises embeddings that do not depend on the batch an image arrives in
+        # (ConvParams::fine) and promises embeddings that do not depend on the batch an image arrives in.
+        # First pass with the latency form off, so that the comparison is made on launches the linear-tile kernel itself
+        # served (asserted from the entry's report); second pass in the library's setting, where the few-image cases with
+        # Cin >= 128 go to conv3x3_lat_kernel — bit-equal again, to each other and to the first pass.
+        kernel = {7: LIN7, 14: LIN14, 28: LIN28, 56: LIN56}[W]
         forms = []
-        for fine in (0, 1):
-            out.fill_(float("nan"))
-            gpu.check(lib.alink_conv_nhwc(gpu.DT_BF16, gpu.ptr(xd), gpu.ptr(wd), gpu.ptr(bd), gpu.ptr(ad), gpu.ptr(rd),
-                                          gpu.ptr(out), N, W, W, Ci, Co, 3, 1, 1, border, fine, None), "alink_conv_nhwc")
-            forms.append(out.clone())
-        assert torch.equal(forms[0].view(torch.int16), forms[1].view(torch.int16)), (case, N, W, Ci, Co)
+        try:
+            for latency in (0, 1600):
+                lib.alink_debug_set_latency_form(latency)
+                for fine in (0, 1):
+                    out.fill_(float("nan"))
+                    kern, form = C.c_int(-1), C.c_int(-1)
+                    gpu.check(lib.alink_conv_nhwc_ex(gpu.DT_BF16, gpu.ptr(xd), gpu.ptr(wd), gpu.ptr(bd), gpu.ptr(ad), gpu.ptr(rd),
+                                                     gpu.ptr(out), N, W, W, Ci, Co, 3, 1, 1, border, fine,
+                                                     0, None, 0, None, None, 0, 0, 1, C.byref(kern), C.byref(form), None),
+                              "alink_conv_nhwc_ex")
+                    assert kern.value == kernel, (case, N, W, Ci, Co, kern.value)
+                    if latency == 0:
+                        assert form.value == SELF, (case, N, W, Ci, Co, form.value)
+                    else:
+                        n_lat += form.value == LAT3X3
+                    forms.append(out.clone())
+        finally:
+            lib.alink_debug_set_latency_form(1600)
+        for f in forms[1:]:
+            assert torch.equal(forms[0].view(torch.int16), f.view(torch.int16)), (case, N, W, Ci, Co)
         got = out.float().cpu()
         assert torch.isfinite(got).all(), (case, N, W, Ci, Co)
         err = (got - ref).abs()
         tol = 2.0 ** -8 * ref.abs() + 2e-3
         assert (err <= tol).all(), "case %d N=%d W=%d Ci=%d Co=%d border=%d: excess %.4g" % (
             case, N, W, Ci, Co, border, float((err - tol).max()))
+    assert n_lat > 0, "no fuzz case reached the latency form in the library's setting"

@@ -20,6 +20,7 @@
 //     full bias minus the per-tap shift contributions of the taps that fall outside the image.
 //   * final bn1 + fc1 BN fold into the FC weights/bias (no padding there).
 #include "alink_common.h"
+#include "net_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -52,26 +53,12 @@ uint16_t f32_to_bf16_rne(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
-uint16_t f32_to_f16_rne(float f) {
+// (never inlined: next to a caller's (float)v the compiler may round v to f16 directly, which is cvt's Round16::Direct, not this)
+__attribute__((noinline)) uint16_t f32_to_f16_rne(float f) {
     _Float16 h = (_Float16)f;   // host clang: IEEE RNE conversion
     uint16_t u;
     memcpy(&u, &h, 2);
     return u;
-}
-static inline uint16_t cvt(int dtype, float f) {
-    return dtype == ALINK_DT_BF16 ? f32_to_bf16_rne(f) : f32_to_f16_rne(f);
-}
-// ALINK_DT_F16X2: x -> f16 pair, hi = RN16(x), lo = RN16(x - hi): |x - hi - lo| <= 2^-22 |x| (while lo stays normal)
-static inline void split16(double x, uint16_t* hi, uint16_t* lo) {
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (double)h);
-    memcpy(hi, &h, 2);
-    memcpy(lo, &l, 2);
-}
-// exponent e with maxabs * 2^e in [1024, 2048): 32x below the f16 overflow threshold, lo = 2^-11 hi still >= 2^-1
-static inline int scale_exp(double maxabs) {
-    if (!(maxabs > 0.0) || !std::isfinite(maxabs)) return 0;
-    return 10 - std::ilogb(maxabs);
 }
 
 hipError_t conv_set_attributes();
@@ -126,9 +113,9 @@ extern "C" void alink_debug_set_fuse_shortcut(int on) { g_fuse_shortcut = on != 
 struct alink_backbone {
     int device = -1;                                           // device of every allocation / stream of this handle
     alink_ir_cfg cfg;
-    std::vector<std::pair<std::string, size_t>> expected;     // name, count (load order)
-    std::map<std::string, std::vector<float>> raw;
+    TensorTable tensors;                                       // MXNet names, load order
     bool finalized = false;
+    DeviceAllocs mem;
 
     // device side
     void*  d_stem_w = nullptr;
@@ -147,18 +134,14 @@ struct alink_backbone {
     bool front_slopes_le_1 = false;   // no PReLU slope of the stem or of stage1_unit1 conv1 exceeds 1 (front_c64.hip: PReLU as a max)
     bool fuse_shortcut = true;  // alink_debug_set_fuse_shortcut (A/B): projection shortcuts inside the conv2 launch
     F32Net* f32 = nullptr;      // cfg.dtype == ALINK_DT_F32: the float32 precision mode (backbone_f32.hip) runs every call
-    // ALINK_DT_F16X2 (split precision)
-    bool calibrated = false;
+    // ALINK_DT_F16X2 (split precision); cal.h_flag / d_flag: set by fc_finish when an embedding is not finite
+    ScaleCalibration cal;
     int  products = 3;                      // split precision: matrix-core products per multiplication (alink_backbone_set_products)
     int  stem_e_w = 0, stem_e_out = 0, fc_e_w = 0;
-    unsigned* d_absmax = nullptr;           // calibration scratch: bits of the largest |value| of a tensor
-    int* h_flag = nullptr;                  // pinned, device-visible: set by fc_finish when an embedding is not finite
-    int* d_flag = nullptr;                  // the same word as the device addresses it
     void*  d_fc_wb = nullptr;                                  // T [C*Hf*Wf][emb]: FC transposed (rows permuted)
     float* d_stem_wf = nullptr;                                // f32 [64][27] folded stem weights
     float* d_zero_bias = nullptr;                              // zeros, >= 9 * max width floats
     int n_units = 0;
-    std::vector<void*> allocs;
     // Optional sub-batch streams (alink_backbone_set_streams): one call is split into image shards on
     // internal streams.  Measured: pays only when shards from SEVERAL calls overlap without a join
     // (host code pipelines 256-image chunks over streams instead — backbone.py); within one call the
@@ -171,20 +154,18 @@ struct alink_backbone {
 
     ~alink_backbone() {
         if (f32) f32net_destroy(f32);
-        for (void* p : allocs) (void)hipFree(p);
         for (int i = 0; i < MAXSUB; ++i) {
             if (sub[i]) (void)hipStreamDestroy(sub[i]);
             if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
             if (ev_front[i]) (void)hipEventDestroy(ev_front[i]);
         }
         if (ev_start) (void)hipEventDestroy(ev_start);
-        if (h_flag) (void)hipHostFree(h_flag);
     }
 };
 
 namespace {
 
-void expect(alink_backbone* bb, const std::string& n, size_t c) { bb->expected.emplace_back(n, c); }
+void expect(alink_backbone* bb, const std::string& n, size_t c) { bb->tensors.expect(n, c); }
 void expect_bn(alink_backbone* bb, const std::string& n, size_t c) {
     expect(bb, n + "_gamma", c);
     expect(bb, n + "_beta", c);
@@ -195,10 +176,10 @@ void expect_bn(alink_backbone* bb, const std::string& n, size_t c) {
 int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
 BN get_bn(const alink_backbone* bb, const std::string& n, bool fix_gamma) {
-    const auto& g = bb->raw.at(n + "_gamma");
-    const auto& be = bb->raw.at(n + "_beta");
-    const auto& mu = bb->raw.at(n + "_moving_mean");
-    const auto& var = bb->raw.at(n + "_moving_var");
+    const auto& g = bb->tensors.at(n + "_gamma");
+    const auto& be = bb->tensors.at(n + "_beta");
+    const auto& mu = bb->tensors.at(n + "_moving_mean");
+    const auto& var = bb->tensors.at(n + "_moving_var");
     BN r;
     r.a.resize(g.size());
     r.b.resize(g.size());
@@ -208,14 +189,6 @@ BN get_bn(const alink_backbone* bb, const std::string& n, bool fix_gamma) {
         r.b[i] = (double)be[i] - (double)mu[i] * r.a[i];
     }
     return r;
-}
-
-template <typename V>
-int upload(alink_backbone* bb, const std::vector<V>& h, void** d) {
-    ALINK_HIP(hipMalloc(d, h.size() * sizeof(V)));
-    bb->allocs.push_back(*d);
-    ALINK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(V), hipMemcpyHostToDevice));
-    return ALINK_OK;
 }
 
 // Fold + upload one convolution.  w is MXNet (O, I, kh, kw).
@@ -228,37 +201,21 @@ int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, co
     // split precision: the linear-tile kernel where it applies, the implicit-GEMM kernel everywhere else
     L.kernel = x2 ? linear_variant_x2(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout)
                   : direct_variant(L.ksz, L.stride, L.pad, L.Hin, L.Win, L.Cin, L.Cout);
-    const WeightLayout wl = weight_layout(L.kernel, k, I, x2, I2);
-    std::vector<uint16_t> wq(wl.size(O));
+    // the value: the weight scaled by the BN before (per input channel) and after (per output channel) it
+    auto folded = [&](int co, int tap, int ci) {
+        return post.a[co] * (double)w[((size_t)co * I + ci) * k * k + tap] * (pre ? pre->a[ci] : 1.0);
+    };
+    // fused shortcut: conv1sc (O, I2, 1, 1) scaled by its own BN, behind the taps of the same row
+    const PackedWeights wq = pack_conv_weights(weight_layout(L.kernel, k, I, x2, I2), dt, Round16::Direct, O, folded,
+                                               [&](int co, int ci) { return post_sc->a[co] * (double)(*w_sc)[(size_t)co * I2 + ci]; });
+    L.e_w = wq.e_w;
     std::vector<double> tapb((size_t)k * k * O, 0.0);          // [tap][co] shift contribution
-    if (x2) {
-        double mx = 0.0;
-        for (int co = 0; co < O; ++co)
-            for (int ci = 0; ci < I; ++ci)
-                for (int t = 0; t < k * k; ++t)
-                    mx = std::max(mx, std::fabs(post.a[co] * (double)w[((size_t)co * I + ci) * k * k + t] * (pre ? pre->a[ci] : 1.0)));
-        L.e_w = scale_exp(mx);
-    }
-    const double wscale = std::ldexp(1.0, L.e_w);
-    for (int co = 0; co < O; ++co) {
-        for (int ky = 0; ky < k; ++ky)
-            for (int kx = 0; kx < k; ++kx) {
-                double tb = 0.0;
-                for (int ci = 0; ci < I; ++ci) {
-                    const double wv = (double)w[(((size_t)co * I + ci) * k + ky) * k + kx];
-                    const double ai = pre ? pre->a[ci] : 1.0;
-                    // the value: the weight scaled by the BN before (per input channel) and after (per output channel) it
-                    const size_t at = wl.at(co, ky * k + kx, ci);
-                    if (x2) split16(post.a[co] * wv * ai * wscale, &wq[at], &wq[at + wl.lo_offset()]);
-                    else    wq[at] = cvt(dt, (float)(post.a[co] * wv * ai));
-                    if (pre) tb += wv * pre->b[ci];
-                }
-                tapb[(size_t)(ky * k + kx) * O + co] = post.a[co] * tb;
-            }
-        // fused shortcut: conv1sc (O, I2, 1, 1) scaled by its own BN, behind the taps of the same row
-        for (int ci = 0; ci < I2; ++ci)
-            wq[wl.at_shortcut(co, ci)] = cvt(dt, (float)(post_sc->a[co] * (double)(*w_sc)[(size_t)co * I2 + ci]));
-    }
+    for (int co = 0; co < O; ++co)
+        for (int t = 0; t < k * k; ++t) {
+            double tb = 0.0;
+            for (int ci = 0; pre && ci < I; ++ci) tb += (double)w[((size_t)co * I + ci) * k * k + t] * pre->b[ci];
+            tapb[(size_t)t * O + co] = post.a[co] * tb;
+        }
     const int ncls = L.border_cls ? 9 : 1;
     std::vector<float> bias((size_t)ncls * O);
     for (int co = 0; co < O; ++co) {
@@ -278,10 +235,10 @@ int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, co
             }
     }
     int rc;
-    if ((rc = upload(bb, wq, &L.d_w))) return rc;
-    if ((rc = upload(bb, bias, (void**)&L.d_bias))) return rc;
+    if ((rc = bb->mem.upload(wq.w, &L.d_w))) return rc;
+    if ((rc = bb->mem.upload(bias, (void**)&L.d_bias))) return rc;
     if (prelu) {
-        if ((rc = upload(bb, *prelu, (void**)&L.d_alpha))) return rc;
+        if ((rc = bb->mem.upload(*prelu, (void**)&L.d_alpha))) return rc;
     }
     if (bb->grad) {
         // d(input) = conv(d(output), Wb): Wb[ci][tap'][co] = Wfolded[co][k*k-1-tap'][ci].  The backward
@@ -289,18 +246,7 @@ int build_conv(alink_backbone* bb, ConvLayer& L, const std::vector<float>& w, co
         // zero-inserted d(output)), with the layer's own padding.
         const int Hb = (L.ksz == 3) ? L.Hin : L.Hout, Wb = (L.ksz == 3) ? L.Win : L.Wout;
         L.bkernel = direct_variant_tiles(L.ksz, 1, L.pad, Hb, Wb, O, I);
-        const WeightLayout bl = weight_layout(L.bkernel, k, O);
-        std::vector<uint16_t> wb(bl.size(I));
-        for (int ci = 0; ci < I; ++ci)
-            for (int tap = 0; tap < k * k; ++tap) {
-                const int ft = k * k - 1 - tap, ky = ft / k, kx = ft % k;
-                for (int co = 0; co < O; ++co) {
-                    const double wv = (double)w[(((size_t)co * I + ci) * k + ky) * k + kx];
-                    const double ai = pre ? pre->a[ci] : 1.0;
-                    wb[bl.at(ci, tap, co)] = cvt(dt, (float)(post.a[co] * wv * ai));
-                }
-            }
-        if ((rc = upload(bb, wb, &L.d_wb))) return rc;
+        if ((rc = bb->mem.upload(pack_conv_weights_backward(weight_layout(L.bkernel, k, O), dt, Round16::Direct, I, folded), &L.d_wb))) return rc;
     }
     return ALINK_OK;
 }
@@ -391,27 +337,16 @@ void alink_backbone_destroy(alink_backbone_t* bb) {
     delete bb;
 }
 
-int alink_backbone_num_tensors(const alink_backbone_t* bb) { return bb ? (int)bb->expected.size() : 0; }
+int alink_backbone_num_tensors(const alink_backbone_t* bb) { return bb ? bb->tensors.count() : 0; }
 
 int alink_backbone_tensor_info(const alink_backbone_t* bb, int i, const char** name, size_t* count) {
-    ALINK_REQUIRE(bb && i >= 0 && i < (int)bb->expected.size(), ALINK_EINVAL, "tensor index out of range");
-    if (name) *name = bb->expected[i].first.c_str();
-    if (count) *count = bb->expected[i].second;
-    return ALINK_OK;
+    ALINK_REQUIRE(bb, ALINK_EINVAL, "tensor index out of range");
+    return bb->tensors.info(i, name, count);
 }
 
 int alink_backbone_load(alink_backbone_t* bb, const char* name, const float* host, size_t count) {
-    ALINK_REQUIRE(bb && name && host, ALINK_EINVAL, "NULL argument");
-    ALINK_REQUIRE(!bb->finalized, ALINK_ESTATE, "backbone already finalized");
-    for (const auto& e : bb->expected)
-        if (e.first == name) {
-            ALINK_REQUIRE(e.second == count, ALINK_EINVAL, "tensor %s: expected %zu elements, got %zu", name,
-                          e.second, count);
-            bb->raw[name].assign(host, host + count);
-            return ALINK_OK;
-        }
-    set_error("tensor %s is not part of the configured network", name);
-    return ALINK_ENOTFOUND;
+    ALINK_REQUIRE(bb, ALINK_EINVAL, "NULL argument");
+    return bb->tensors.load(name, host, count, bb->finalized, "the configured network", "backbone");
 }
 
 int alink_backbone_finalize(alink_backbone_t* bb) {
@@ -419,47 +354,35 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
     ALINK_REQUIRE(!bb->finalized, ALINK_ESTATE, "backbone already finalized");
     DeviceGuard dg(bb->device);
     { const int rc0 = init_kernels(); if (rc0) return rc0; }
-    for (const auto& e : bb->expected)
-        ALINK_REQUIRE(bb->raw.count(e.first), ALINK_ESTATE, "tensor %s was never loaded", e.first.c_str());
+    int rc = bb->tensors.require_all_loaded();
+    if (rc) return rc;
     if (bb->grad)   // the backward pass tells the PReLU side from the sign of the stored activation
-        for (const auto& e : bb->expected)
+        for (const auto& e : bb->tensors.expected)
             if (e.first.find("relu") != std::string::npos)
-                for (float a : bb->raw.at(e.first))
+                for (float a : bb->tensors.at(e.first))
                     ALINK_REQUIRE(a >= 0.f, ALINK_EINVAL, "%s has a negative PReLU slope: input gradients are not "
                                   "supported for this checkpoint", e.first.c_str());
-    int rc = init_kernels();
-    if (rc) return rc;
     const alink_ir_cfg& cfg = bb->cfg;
     const int dt = cfg.dtype;
     const int* w = cfg.widths;
     if (dt == ALINK_DT_F32) {      // float32 precision mode: its own (unfused-bn1, f32 GEMM) network, nothing of the bf16 path
         ALINK_REQUIRE(!bb->grad && !bb->split_small, ALINK_ESTATE, "the float32 mode has no gradient pass and no small-batch split");
-        bb->f32 = f32net_build(bb->raw, cfg);
+        bb->f32 = f32net_build(bb->tensors.raw, cfg);
         ALINK_REQUIRE(bb->f32, ALINK_ENOMEM, "could not build the float32 network (device memory)");
-        bb->raw.clear();
+        bb->tensors.clear();
         bb->finalized = true;
         return ALINK_OK;
     }
 
     const bool x2 = dt == ALINK_DT_F16X2;
-    if (x2) {
-        ALINK_REQUIRE(!bb->grad, ALINK_ESTATE, "the split-precision mode has no gradient pass");
-        ALINK_HIP(hipMalloc((void**)&bb->d_absmax, 256));
-        bb->allocs.push_back(bb->d_absmax);
-    }
-    ALINK_HIP(hipHostMalloc((void**)&bb->h_flag, 64, hipHostMallocMapped));
-    *bb->h_flag = 0;
-    ALINK_HIP(hipHostGetDevicePointer((void**)&bb->d_flag, bb->h_flag, 0));
-
-    // zero page
-    ALINK_HIP(hipMalloc(&bb->d_zero, 4096));
-    bb->allocs.push_back(bb->d_zero);
-    ALINK_HIP(hipMemset(bb->d_zero, 0, 4096));
+    ALINK_REQUIRE(!x2 || !bb->grad, ALINK_ESTATE, "the split-precision mode has no gradient pass");
+    if ((rc = bb->cal.init(bb->mem, x2))) return rc;
+    if ((rc = bb->mem.zeros(4096, &bb->d_zero))) return rc;      // zero page
 
     // ---- stem: W'[co][k=ky*9+kx*3+c] = a0[co] * W[co][c][ky][kx]; input normalisation happens in
     // the kernel's loader so the zero frame is a true zero and no border classes are needed.
     {
-        const auto& cw = bb->raw.at("conv0_weight");
+        const auto& cw = bb->tensors.at("conv0_weight");
         const BN bn0 = get_bn(bb, "bn0", false);
         // 16-bit modes: K = 64 in two MFMA steps, [ky 0: kx*3+c (9) + 7 zeros | ky 1: the same] [ky 2: the same | 16 zeros] — a
         // pixel's window of one row is one aligned 32-byte record for the fused front kernel (front_c64.hip), and stem_kernel
@@ -479,18 +402,18 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
                         const double v = bn0.a[co] * (double)cw[(((size_t)co * 3 + c) * 3 + ky) * 3 + kx];
                         const int kk = ky * 9 + kx * 3 + c;
                         if (x2) split16(std::ldexp(v, bb->stem_e_w), &wq[(size_t)row * 64 + kk], &wq[(size_t)row * 64 + 32 + kk]);
-                        else    wq[(size_t)row * 64 + ky * 16 + kx * 3 + c] = cvt(dt, (float)v);
+                        else    wq[(size_t)row * 64 + ky * 16 + kx * 3 + c] = cvt(dt, v, Round16::Direct);
                     }
         }
         std::vector<float> bias(64);
         for (int co = 0; co < 64; ++co) bias[co] = (float)bn0.b[co];
-        if ((rc = upload(bb, wq, &bb->d_stem_w))) return rc;
-        if ((rc = upload(bb, bias, (void**)&bb->d_stem_bias))) return rc;
-        if ((rc = upload(bb, bb->raw.at("relu0_gamma"), (void**)&bb->d_stem_alpha))) return rc;
+        if ((rc = bb->mem.upload(wq, &bb->d_stem_w))) return rc;
+        if ((rc = bb->mem.upload(bias, (void**)&bb->d_stem_bias))) return rc;
+        if ((rc = bb->mem.upload(bb->tensors.at("relu0_gamma"), (void**)&bb->d_stem_alpha))) return rc;
         bb->front_slopes_le_1 = true;
         for (const char* nm : {"relu0_gamma", "stage1_unit1_relu1_gamma"})
-            if (bb->raw.count(nm))
-                for (float a : bb->raw.at(nm)) bb->front_slopes_le_1 = bb->front_slopes_le_1 && a <= 1.f;
+            if (bb->tensors.raw.count(nm))
+                for (float a : bb->tensors.at(nm)) bb->front_slopes_le_1 = bb->front_slopes_le_1 && a <= 1.f;
         if (bb->grad) {
             std::vector<float> wf((size_t)64 * 27);
             for (int co = 0; co < 64; ++co)
@@ -499,9 +422,9 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
                         for (int kx = 0; kx < 3; ++kx)
                             wf[(size_t)co * 27 + ky * 9 + kx * 3 + c] =
                                 (float)(bn0.a[co] * (double)cw[(((size_t)co * 3 + c) * 3 + ky) * 3 + kx]);
-            if ((rc = upload(bb, wf, (void**)&bb->d_stem_wf))) return rc;
-            std::vector<float> zb(std::max((size_t)9 * 2048, (size_t)cfg.widths[4] * (cfg.height / 16) * (cfg.width / 16)), 0.f);
-            if ((rc = upload(bb, zb, (void**)&bb->d_zero_bias))) return rc;
+            if ((rc = bb->mem.upload(wf, (void**)&bb->d_stem_wf))) return rc;
+            const size_t zb = std::max((size_t)9 * 2048, (size_t)cfg.widths[4] * (cfg.height / 16) * (cfg.width / 16));
+            if ((rc = bb->mem.zeros(zb * sizeof(float), (void**)&bb->d_zero_bias))) return rc;
         }
     }
 
@@ -534,7 +457,7 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
             c1.Hin = H; c1.Win = W; c1.Hout = H; c1.Wout = W;
             c1.border_cls = true; c1.has_alpha = true;
             c1.in_buf = xb; c1.out_buf = tb; c1.resid_buf = -1; c1.role = 1; c1.unit = bb->n_units; c1.stage = s;
-            if ((rc = build_conv(bb, c1, bb->raw.at(P + "_conv1_weight"), &bn1, bn2, &bb->raw.at(P + "_relu1_gamma"))))
+            if ((rc = build_conv(bb, c1, bb->tensors.at(P + "_conv1_weight"), &bn1, bn2, &bb->tensors.at(P + "_relu1_gamma"))))
                 return rc;
             bb->convs.push_back(c1);
 
@@ -551,7 +474,7 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
                 sc.Hin = H; sc.Win = W; sc.Hout = Ho; sc.Wout = Wo;
                 sc.border_cls = false; sc.has_alpha = false;
                 sc.in_buf = xb; sc.out_buf = sb; sc.resid_buf = -1; sc.role = 2; sc.unit = bb->n_units; sc.stage = s;
-                if ((rc = build_conv(bb, sc, bb->raw.at(P + "_conv1sc_weight"), nullptr, bsc, nullptr))) return rc;
+                if ((rc = build_conv(bb, sc, bb->tensors.at(P + "_conv1sc_weight"), nullptr, bsc, nullptr))) return rc;
                 bb->convs.push_back(sc);
                 resid = sb;
             }
@@ -564,10 +487,10 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
             if (fuse_sc) {
                 const BN bsc = get_bn(bb, P + "_sc", false);
                 c2.resid_buf = -1; c2.Cin2 = cin; c2.in2_buf = xb;
-                if ((rc = build_conv(bb, c2, bb->raw.at(P + "_conv2_weight"), nullptr, bn3, nullptr, &bb->raw.at(P + "_conv1sc_weight"), &bsc)))
+                if ((rc = build_conv(bb, c2, bb->tensors.at(P + "_conv2_weight"), nullptr, bn3, nullptr, &bb->tensors.at(P + "_conv1sc_weight"), &bsc)))
                     return rc;
             } else
-            if ((rc = build_conv(bb, c2, bb->raw.at(P + "_conv2_weight"), nullptr, bn3, nullptr))) return rc;
+            if ((rc = build_conv(bb, c2, bb->tensors.at(P + "_conv2_weight"), nullptr, bn3, nullptr))) return rc;
             bb->convs.push_back(c2);
             ++bb->n_units;
             xb = yb;
@@ -579,8 +502,8 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
     // ---- FC: flatten is (C,H,W) in the reference symbol; our activations are (H,W,C).
     {
         const int C = w[4], E = cfg.emb, HW = H * W, K = C * HW;
-        const auto& fw = bb->raw.at("pre_fc1_weight");
-        const auto& fb = bb->raw.at("pre_fc1_bias");
+        const auto& fw = bb->tensors.at("pre_fc1_weight");
+        const auto& fb = bb->tensors.at("pre_fc1_bias");
         const BN bnl = get_bn(bb, "bn1", false), bfc = get_bn(bb, "fc1", true);
         std::vector<uint16_t> wq((size_t)E * K * (x2 ? 2 : 1));
         std::vector<float> bias(E);
@@ -603,14 +526,14 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
                         const size_t khi = (kk >> 6) * 128 + (kk & 63);
                         split16(std::ldexp(bfc.a[o] * wv * bnl.a[ch], bb->fc_e_w), &wq[(size_t)row * 2 * K + khi], &wq[(size_t)row * 2 * K + khi + 64]);
                     } else {
-                        wq[(size_t)row * K + kk] = cvt(dt, (float)(bfc.a[o] * wv * bnl.a[ch]));
+                        wq[(size_t)row * K + kk] = cvt(dt, bfc.a[o] * wv * bnl.a[ch], Round16::Direct);
                     }
                     b += wv * bnl.b[ch];
                 }
             bias[o] = (float)(bfc.a[o] * b + bfc.b[o]);
         }
-        if ((rc = upload(bb, wq, &bb->d_fc_w))) return rc;
-        if ((rc = upload(bb, bias, (void**)&bb->d_fc_bias))) return rc;
+        if ((rc = bb->mem.upload(wq, &bb->d_fc_w))) return rc;
+        if ((rc = bb->mem.upload(bias, (void**)&bb->d_fc_bias))) return rc;
         if (bb->grad) {
             // d(x4)[pos][ch] = sum_o d(z)[o] * Wfolded[o][pos][ch]: a 1x1 "convolution" emb -> C*H*W
             std::vector<uint16_t> wb((size_t)K * E);
@@ -619,10 +542,10 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
                 const size_t row = (size_t)((kk & ~63) + perm64_row_of_channel(kk & 63)) * E;
                 for (int o = 0; o < E; ++o) {
                     const double wv = (double)fw[(size_t)o * K + (size_t)ch * HW + pos];
-                    wb[row + o] = cvt(dt, (float)(bfc.a[o] * wv * bnl.a[ch]));
+                    wb[row + o] = cvt(dt, bfc.a[o] * wv * bnl.a[ch], Round16::Direct);
                 }
             }
-            if ((rc = upload(bb, wb, &bb->d_fc_wb))) return rc;
+            if ((rc = bb->mem.upload(wb, &bb->d_fc_wb))) return rc;
         }
         bb->fc_K = K;
         const int nk = K / 64;
@@ -640,7 +563,7 @@ int alink_backbone_finalize(alink_backbone_t* bb) {
         ALINK_HIP(hipEventCreateWithFlags(&bb->ev_front[i], hipEventDisableTiming));
     }
     ALINK_HIP(hipEventCreateWithFlags(&bb->ev_start, hipEventDisableTiming));
-    bb->raw.clear();
+    bb->tensors.clear();
     bb->finalized = true;
     return ALINK_OK;
 }
@@ -852,16 +775,9 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
     const int reps = prof ? g_prof_reps : 1;
     const int cap = prof ? *n_launches : 0;
     int nl = 0;
-    std::vector<hipEvent_t> ev;
+    LaunchTimer timer(prof);
     std::vector<int> split_pairs;     // profile entries i, i + 1 that share one launch (a fused unit's conv1 and conv2)
-    auto mark = [&]() -> int {
-        if (!prof) return ALINK_OK;
-        hipEvent_t e;
-        ALINK_HIP(hipEventCreate(&e));
-        ALINK_HIP(hipEventRecord(e, stream));
-        ev.push_back(e);
-        return ALINK_OK;
-    };
+    auto mark = [&]() -> int { return timer.mark(stream); };
     auto note = [&](double f, int k) {
         if (prof && nl < cap) { flops[nl] = f; kind[nl] = k; }
         ++nl;
@@ -871,34 +787,8 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
 
     const bool x2 = cfg.dtype == ALINK_DT_F16X2;
     ALINK_REQUIRE(!calib || x2, ALINK_ESTATE, "only the split-precision mode is calibrated");
-    ALINK_REQUIRE(!x2 || calib || bb->calibrated, ALINK_ESTATE, "split-precision backbone: alink_backbone_calibrate has not run");
+    ALINK_REQUIRE(!x2 || calib || bb->cal.calibrated, ALINK_ESTATE, "split-precision backbone: alink_backbone_calibrate has not run");
     int bexp[5] = {0, 0, 0, 0, 0};        // split precision: scale exponent of the tensor each workspace buffer holds
-    // calibration: run `launch(e)` with the output exponent e until the largest |output| lies in [1024, 2048) (f16 pairs:
-    // 32x below overflow, lo halves normal); a power-of-two scale changes no bit of the result, only where it sits
-    auto settle = [&](int* e_io, const void* out, size_t n_elems, auto&& launch) -> int {
-        int e = *e_io;
-        for (int attempt = 0; attempt < 24; ++attempt) {
-            const int rcl = launch(e);
-            if (rcl) return rcl;
-            if (!calib) break;
-            unsigned bits = 0;
-            ALINK_HIP(hipMemsetAsync(bb->d_absmax, 0, 4, stream));
-            ALINK_HIP(launch_absmax_f16(out, n_elems, bb->d_absmax, stream));
-            ALINK_HIP(hipMemcpyAsync(&bits, bb->d_absmax, 4, hipMemcpyDeviceToHost, stream));
-            ALINK_HIP(hipStreamSynchronize(stream));
-            float m;
-            memcpy(&m, &bits, 4);
-            if (bits >= 0x7f800000u) { e -= 8; continue; }                 // left the range: lower the scale and redo
-            if (m == 0.f) break;
-            int want = e + (10 - std::ilogb(m));
-            if (calib == 2 && bb->calibrated) want = std::min(want, *e_io);
-            if (want == e) break;
-            e = want;
-        }
-        *e_io = e;
-        return ALINK_OK;
-    };
-
     StemParams sp{};
     sp.in = dev_in; sp.wgt = bb->d_stem_w; sp.bias = bb->d_stem_bias; sp.alpha = bb->d_stem_alpha;
     sp.out = buf(0); sp.N = N; sp.H = cfg.height; sp.W = cfg.width; sp.C0 = 64; sp.layout = layout;
@@ -914,7 +804,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
     if (front) {
         // launched with conv1 below
     } else if (x2) {
-        rc = settle(&bb->stem_e_out, buf(0), (size_t)N * cfg.height * cfg.width * 128, [&](int e) -> int {
+        rc = bb->cal.settle(calib, &bb->stem_e_out, buf(0), (size_t)N * cfg.height * cfg.width * 128, stream, [&](int e) -> int {
             sp.acc_scale = std::ldexp(1.f, e - 8 - bb->stem_e_w);          // the loader stores normalised pixels x 2^8
             sp.bias_scale = std::ldexp(1.f, e);
             for (int r = 0; r < reps; ++r) ALINK_HIP(launch_stem(cfg.dtype, sp, stream));
@@ -948,10 +838,8 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             if (L.role == 1) p.out = base + cache->toff[L.unit];
             if (L.role == 3) p.in = base + cache->toff[L.unit];
         }
-        p.N = N; p.H = L.Hin; p.W = L.Win; p.Cin = L.Cin; p.Cout = L.Cout; p.Ho = L.Hout; p.Wo = L.Wout;
-        p.stride = L.stride; p.ksz = L.ksz; p.pad = L.pad; p.M = N * L.Hout * L.Wout;
-        p.border_cls = L.border_cls ? 1 : 0; p.splitk = 1;
-        p.ksteps_per_split = L.ksz * L.ksz * (L.Cin / 64) + L.Cin2 / 64;
+        conv_geometry(p, N, L.Hin, L.Win, L.Cin, L.Cout, L.ksz, L.stride, L.pad, L.Cin2, x2);
+        p.border_cls = L.border_cls ? 1 : 0;
         if (L.Cin2) { p.in2 = buf(L.in2_buf); p.Cin2 = L.Cin2; p.in2_compact = (front && &L == &bb->convs[1]) ? 1 : 0; }
         p.ablate = g_ablate;
         p.stagger = g_stagger;
@@ -965,19 +853,12 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             if (traits(L.kernel).split == SplitUnit::Chunk ? conv3x3_lat_applies(cfg.dtype, probe) : conv_gemm_lat_applies(cfg.dtype, probe)) S = 1;
         }
         if (x2) {
-            p.ksteps_per_split *= 3;
-            rc = settle(&L.e_out, p.out, (size_t)p.M * L.Cout * 2, [&](int e) -> int {
+            rc = bb->cal.settle(calib, &L.e_out, p.out, (size_t)p.M * L.Cout * 2, stream, [&](int e) -> int {
                 p.acc_scale = std::ldexp(1.f, e - bexp[L.in_buf] - L.e_w);
                 p.bias_scale = std::ldexp(1.f, e);
                 p.res_scale = L.resid_buf >= 0 ? std::ldexp(1.f, e - bexp[L.resid_buf]) : 1.f;
-                for (int r = 0; r < reps; ++r) {
-                    ConvParams q = p;
-                    if (S > 1) {           // latency mode: K split into f32 slabs of raw accumulators, scales applied by the finish kernel
-                        q.out = buf(6); q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S;
-                    }
-                    ALINK_HIP(launch_conv(L.kernel, cfg.dtype, q, stream));
-                    if (S > 1) ALINK_HIP(launch_conv_split_finish(cfg.dtype, p, (const float*)buf(6), S, stream));
-                }
+                // (S > 1, latency mode: K split into f32 slabs of raw accumulators, scales applied by the finish kernel)
+                for (int r = 0; r < reps; ++r) ALINK_HIP(launch_conv_maybe_split(L.kernel, cfg.dtype, p, S, buf(6), stream));
                 return ALINK_OK;
             });
             if (rc) return rc;
@@ -987,10 +868,9 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             const ConvLayer& L2 = bb->convs[1];
             ConvParams p2 = p;
             p2.in = buf(L2.in_buf); p2.wgt = L2.d_w; p2.bias = L2.d_bias; p2.alpha = L2.d_alpha; p2.resid = nullptr;
-            p2.out = buf(L2.out_buf); p2.Cout = L2.Cout; p2.Ho = L2.Hout; p2.Wo = L2.Wout; p2.stride = L2.stride;
-            p2.M = N * L2.Hout * L2.Wout; p2.border_cls = L2.border_cls ? 1 : 0;
+            p2.out = buf(L2.out_buf); p2.border_cls = L2.border_cls ? 1 : 0;
+            conv_geometry(p2, N, L2.Hin, L2.Win, L2.Cin, L2.Cout, L2.ksz, L2.stride, L2.pad, L2.Cin2);
             p2.in2 = buf(L2.in2_buf); p2.Cin2 = L2.Cin2; p2.in2_compact = 1;
-            p2.ksteps_per_split = L2.ksz * L2.ksz * (L2.Cin / 64) + L2.Cin2 / 64;
             ALINK_REQUIRE(unit1_c64_applies(cfg.dtype, p, sp, p2), ALINK_EINVAL, "fused unit %s: launch forms do not apply", L.name.c_str());
             for (int r = 0; r < reps; ++r) ALINK_HIP(launch_unit1_c64(cfg.dtype, p, sp, p2, bb->front_slopes_le_1, stream));
             // one profile entry per layer, as for the plain fused units: conv1 (+ stem) and conv2 (+ shortcut), half the time each
@@ -1030,14 +910,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
             skip_conv2 = true;
             continue;
         } else
-        for (int r = 0; r < reps; ++r) {
-            ConvParams q = p;
-            if (S > 1) {
-                q.out = buf(6); q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S;
-            }
-            ALINK_HIP(launch_conv(L.kernel, cfg.dtype, q, stream));
-            if (S > 1) ALINK_HIP(launch_conv_split_finish(cfg.dtype, p, (const float*)buf(6), S, stream));
-        }
+        for (int r = 0; r < reps; ++r) ALINK_HIP(launch_conv_maybe_split(L.kernel, cfg.dtype, p, S, buf(6), stream));
         note(conv_flops(p), 1);
         if ((rc = mark())) return rc;
         last_out = L.out_buf;
@@ -1048,8 +921,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
         ConvParams p{};
         p.in = buf(last_out); p.wgt = bb->d_fc_w; p.bias = nullptr; p.alpha = nullptr; p.resid = nullptr;
         p.out = buf(5); p.zero = bb->d_zero;
-        p.N = N; p.H = 1; p.W = 1; p.Cin = bb->fc_K; p.Cout = cfg.emb; p.Ho = 1; p.Wo = 1;
-        p.stride = 1; p.ksz = 1; p.pad = 0; p.M = N; p.border_cls = 0;
+        conv_geometry(p, N, 1, 1, bb->fc_K, cfg.emb, 1, 1, 0);
         p.splitk = bb->fc_splitk; p.ksteps_per_split = bb->fc_kps * (x2 ? 3 : 1);
         p.nprod = (x2 && !calib) ? bb->products : 0;
         ALINK_REQUIRE(p.splitk > 1, ALINK_EINVAL, "FC split-K must be > 1 (K=%d)", bb->fc_K);
@@ -1061,7 +933,7 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
         f.norms = cache ? (float*)(base + cache->norms) : nullptr;
         f.S = bb->fc_splitk; f.M = N; f.E = cfg.emb;
         f.scale = x2 ? std::ldexp(1.f, -(bexp[last_out] + bb->fc_e_w)) : 1.f;
-        f.nonfinite = bb->d_flag;       // 16-bit storage: an activation beyond the range ends as a non-finite embedding
+        f.nonfinite = bb->cal.d_flag;       // 16-bit storage: an activation beyond the range ends as a non-finite embedding
         for (int r = 0; r < reps; ++r) ALINK_HIP(launch_fc_finish(f, stream));
         note(0.0, 3);
         if ((rc = mark())) return rc;
@@ -1069,20 +941,15 @@ static int embed_impl(alink_backbone_t* bb, const void* dev_in, int layout, int 
 
     if (prof) {
         ALINK_HIP(hipStreamSynchronize(stream));
-        for (int i = 0; i + 1 < (int)ev.size() && i < cap; ++i) {
-            float t = 0.f;
-            ALINK_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            ms[i] = t / (float)reps;
-        }
+        if ((rc = timer.elapsed(ms, cap, reps))) return rc;
         for (int i : split_pairs)
-            if (i + 1 < cap && i + 2 < (int)ev.size()) ms[i] = ms[i + 1] = 0.5f * (ms[i] + ms[i + 1]);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+            if (i + 1 < cap && i + 1 < timer.intervals()) ms[i] = ms[i + 1] = 0.5f * (ms[i] + ms[i + 1]);
         *n_launches = nl;
     }
     if (calib) {
         ALINK_HIP(hipStreamSynchronize(stream));
-        ALINK_REQUIRE(*bb->h_flag == 0, ALINK_EINVAL, "calibration batch produced non-finite embeddings");
-        bb->calibrated = true;
+        ALINK_REQUIRE(*bb->cal.h_flag == 0, ALINK_EINVAL, "calibration batch produced non-finite embeddings");
+        bb->cal.calibrated = true;
     }
     return ALINK_OK;
 }
@@ -1148,10 +1015,7 @@ int alink_backbone_calibrate(alink_backbone_t* bb, const void* dev_in, int layou
     DeviceGuard dg(bb->device);
     hipStream_t st = (hipStream_t)stream;
     ALINK_HIP(hipStreamSynchronize(st));
-    // a report still pending from an earlier forward (lazy range checks read the flag later) must survive the calibration run
-    const int pending = *(volatile int*)bb->h_flag;
-    struct Keep { int* f; int v; ~Keep() { if (v) *(volatile int*)f = 1; } } keep{bb->h_flag, pending};
-    *bb->h_flag = 0;
+    ScaleCalibration::PendingReport keep(bb->cal);
     float* scratch = nullptr;           // the embeddings of the calibration batch are not wanted
     ALINK_HIP(hipMalloc((void**)&scratch, (size_t)n_images * bb->cfg.emb * sizeof(float)));
     const int rc = embed_impl(bb, dev_in, layout, n_images, scratch, dev_workspace, workspace_bytes, st, nullptr, nullptr,
@@ -1165,38 +1029,24 @@ int alink_backbone_num_scales(const alink_backbone_t* bb) {
     return 1 + (int)bb->convs.size();
 }
 
+// exponent i of the network: the stem's output, then every convolution's
 int alink_backbone_get_scales(const alink_backbone_t* bb, int* exponents, int n) {
     ALINK_REQUIRE(bb && bb->finalized, ALINK_ESTATE, "alink_backbone_get_scales before alink_backbone_finalize");
-    ALINK_REQUIRE(bb->cfg.dtype == ALINK_DT_F16X2, ALINK_ESTATE, "only the split-precision mode (ALINK_DT_F16X2) has scales");
-    ALINK_REQUIRE(bb->calibrated, ALINK_ESTATE, "alink_backbone_get_scales before alink_backbone_calibrate / set_scales");
-    ALINK_REQUIRE(exponents && n == 1 + (int)bb->convs.size(), ALINK_EINVAL, "expected room for %d exponents, got %d",
-                  1 + (int)bb->convs.size(), n);
-    exponents[0] = bb->stem_e_out;
-    for (size_t i = 0; i < bb->convs.size(); ++i) exponents[1 + i] = bb->convs[i].e_out;
-    return ALINK_OK;
+    return bb->cal.get_scales("backbone", bb->cfg.dtype == ALINK_DT_F16X2, 1 + (int)bb->convs.size(),
+                              [bb](int i) { return i == 0 ? bb->stem_e_out : bb->convs[i - 1].e_out; }, exponents, n);
 }
 
 int alink_backbone_set_scales(alink_backbone_t* bb, const int* exponents, int n) {
     ALINK_REQUIRE(bb && bb->finalized, ALINK_ESTATE, "alink_backbone_set_scales before alink_backbone_finalize");
-    ALINK_REQUIRE(bb->cfg.dtype == ALINK_DT_F16X2, ALINK_ESTATE, "only the split-precision mode (ALINK_DT_F16X2) has scales");
-    ALINK_REQUIRE(exponents && n == 1 + (int)bb->convs.size(), ALINK_EINVAL, "expected %d exponents, got %d",
-                  1 + (int)bb->convs.size(), n);
-    for (int i = 0; i < n; ++i)
-        ALINK_REQUIRE(exponents[i] >= -126 && exponents[i] <= 126, ALINK_EINVAL, "exponent %d of tensor %d is not a float32 power of two", exponents[i], i);
-    bb->stem_e_out = exponents[0];
-    for (size_t i = 0; i < bb->convs.size(); ++i) bb->convs[i].e_out = exponents[1 + i];
-    bb->calibrated = true;
-    return ALINK_OK;
+    return bb->cal.set_scales("tensor", bb->cfg.dtype == ALINK_DT_F16X2, 1 + (int)bb->convs.size(),
+                              [bb](int i) -> int& { return i == 0 ? bb->stem_e_out : bb->convs[i - 1].e_out; }, exponents, n);
 }
 
 int alink_backbone_device(const alink_backbone_t* bb) { return bb ? bb->device : -1; }
 
 int alink_backbone_range_flag(alink_backbone_t* bb, int reset) {
     ALINK_REQUIRE(bb && bb->finalized, ALINK_ESTATE, "alink_backbone_range_flag before alink_backbone_finalize");
-    if (!bb->h_flag) return 0;          // float32 mode: nothing to leave
-    const int v = *(volatile int*)bb->h_flag != 0 ? 1 : 0;
-    if (reset) *(volatile int*)bb->h_flag = 0;
-    return v;
+    return bb->cal.range_flag(reset);       // (float32 mode: no flag, nothing to leave)
 }
 
 // ---- input gradient (FGSM / PGD extension) ------------------------------------------------------------
@@ -1288,8 +1138,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
     {
         ConvParams p{};
         p.in = base + GL.dfc; p.wgt = bb->d_fc_wb; p.bias = bb->d_zero_bias; p.out = G(cur); p.zero = bb->d_zero;
-        p.N = N; p.H = 1; p.W = 1; p.Cin = cfg.emb; p.Cout = bb->fc_K; p.Ho = 1; p.Wo = 1; p.stride = 1; p.ksz = 1;
-        p.pad = 0; p.M = N; p.splitk = 1; p.ksteps_per_split = cfg.emb / 64;
+        conv_geometry(p, N, 1, 1, cfg.emb, bb->fc_K, 1, 1, 0);
         ALINK_HIP(launch_conv_igemm(dt, p, st));
     }
     // 3) residual units in reverse
@@ -1310,8 +1159,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
             ConvParams p{};
             p.in = dy_full; p.wgt = B.d_wb; p.bias = bb->d_zero_bias; p.alpha = A.d_alpha;
             p.dact = base + GL.toff[u]; p.out = G(ids[1]); p.zero = bb->d_zero;
-            p.N = N; p.H = H; p.W = W; p.Cin = c; p.Cout = c; p.Ho = H; p.Wo = W; p.stride = 1; p.ksz = 3; p.pad = 1;
-            p.M = N * H * W; p.splitk = 1; p.ksteps_per_split = 9 * (c / 64);
+            conv_geometry(p, N, H, W, c, c, 3, 1, 1);
             ALINK_HIP(launch_conv(B.bkernel, dt, p, st));
         }
         const void* r = dy;                             // gradient arriving through the shortcut
@@ -1319,8 +1167,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
             const ConvLayer& S = *sc[u];
             ConvParams p{};
             p.in = dy; p.wgt = S.d_wb; p.bias = bb->d_zero_bias; p.out = G(ids[0]); p.zero = bb->d_zero;
-            p.N = N; p.H = Ho; p.W = Wo; p.Cin = c; p.Cout = cin; p.Ho = Ho; p.Wo = Wo; p.stride = 1; p.ksz = 1; p.pad = 0;
-            p.M = N * Ho * Wo; p.splitk = 1; p.ksteps_per_split = c / 64;
+            conv_geometry(p, N, Ho, Wo, c, cin, 1, 1, 0);
             ALINK_HIP(launch_conv_igemm(dt, p, st));
             ALINK_HIP(launch_zero_insert(dt, G(ids[0]), G(ids[2]), N, H, W, Ho, Wo, cin, st));
             r = G(ids[2]);
@@ -1328,8 +1175,7 @@ int alink_embed_input_grad(alink_backbone_t* bb, const float* dev_demb, const fl
         {   // through conv1 (+ bn1, bn2 folded) and add the shortcut gradient
             ConvParams p{};
             p.in = G(ids[1]); p.wgt = A.d_wb; p.bias = bb->d_zero_bias; p.resid = r; p.out = G(ids[3]); p.zero = bb->d_zero;
-            p.N = N; p.H = H; p.W = W; p.Cin = c; p.Cout = cin; p.Ho = H; p.Wo = W; p.stride = 1; p.ksz = 3; p.pad = 1;
-            p.M = N * H * W; p.splitk = 1; p.ksteps_per_split = 9 * (c / 64);
+            conv_geometry(p, N, H, W, c, cin, 3, 1, 1);
             ALINK_HIP(launch_conv(A.bkernel, dt, p, st));
         }
         cur = ids[3];
@@ -1396,16 +1242,25 @@ static int check_extras(ConvKernel kernel, int dtype, int ksz, int Cin, const fl
     return ALINK_OK;
 }
 
-// the launch itself: fused, or S slabs of f32 partial sums and their finish (divided as alink_embed divides)
-static hipError_t launch_conv_maybe_split(ConvKernel kernel, int dtype, const ConvParams& p, int S, float* slabs,
-                                          const ConvExtras& x, hipStream_t st) {
-    ConvParams q = p;
-    if (S > 1) { q.out = slabs; q.splitk = S; q.ksteps_per_split = p.ksteps_per_split / S; }
+// alink_embed's launch (fused, or S slabs and their finish), and the report of what ran for the _ex entries
+static hipError_t launch_conv_reported(ConvKernel kernel, int dtype, const ConvParams& p, int S, float* slabs,
+                                       const ConvExtras& x, hipStream_t st) {
     if (x.kernel) *x.kernel = (int)kernel;
-    if (x.form) *x.form = served_form(kernel, dtype, q);
-    hipError_t e = launch_conv(kernel, dtype, q, st);
-    if (e == hipSuccess && S > 1) e = launch_conv_split_finish(dtype, p, slabs, S, st);
-    return e;
+    if (x.form) *x.form = served_form(kernel, dtype, k_split_of(p, S, slabs));
+    return launch_conv_maybe_split(kernel, dtype, p, S, slabs, st);
+}
+
+// the value a 16-bit storage word stands for (the 16-bit test entry is handed weights already in the storage type)
+static float widen16(int dtype, uint16_t bits) {
+    if (dtype == ALINK_DT_BF16) {
+        const uint32_t u = (uint32_t)bits << 16;
+        float f;
+        memcpy(&f, &u, 4);
+        return f;
+    }
+    _Float16 h;
+    memcpy(&h, &bits, 2);
+    return (float)h;
 }
 
 static int conv_nhwc_impl(int dtype, const void* dev_in, const void* dev_w, const float* dev_bias,
@@ -1426,40 +1281,30 @@ static int conv_nhwc_impl(int dtype, const void* dev_in, const void* dev_w, cons
     hipStream_t st = (hipStream_t)stream;
     const int K = ksz * ksz * Cin, Cin2 = x.in2 ? x.Cin2 : 0;
     // permute weight rows into a private copy (the shortcut's columns behind the taps of the same row)
-    const WeightLayout wl = weight_layout(kernel, ksz, Cin, false, Cin2);
-    std::vector<uint16_t> h((size_t)Cout * K), h2((size_t)Cout * Cin2), hp(wl.size(Cout));
+    std::vector<uint16_t> h((size_t)Cout * K), h2((size_t)Cout * Cin2);
     ALINK_HIP(hipStreamSynchronize(st));
     ALINK_HIP(hipMemcpy(h.data(), dev_w, h.size() * 2, hipMemcpyDeviceToHost));
     if (Cin2) ALINK_HIP(hipMemcpy(h2.data(), x.w2, h2.size() * 2, hipMemcpyDeviceToHost));
-    for (int co = 0; co < Cout; ++co) {
-        for (int tap = 0; tap < ksz * ksz; ++tap)
-            for (int ci = 0; ci < Cin; ++ci) hp[wl.at(co, tap, ci)] = h[(size_t)co * K + (size_t)tap * Cin + ci];
-        for (int ci = 0; ci < Cin2; ++ci) hp[wl.at_shortcut(co, ci)] = h2[(size_t)co * Cin2 + ci];
-    }
+    const std::vector<uint16_t> hp =
+        pack_conv_weights(weight_layout(kernel, ksz, Cin, false, Cin2), dtype, Round16::Direct, Cout,
+                          [&](int co, int tap, int ci) { return (double)widen16(dtype, h[(size_t)co * K + (size_t)tap * Cin + ci]); },
+                          [&](int co, int ci) { return (double)widen16(dtype, h2[(size_t)co * Cin2 + ci]); }).w;
     ConvParams p{};
     p.in = dev_in; p.bias = dev_bias; p.alpha = dev_alpha; p.resid = dev_resid; p.dact = x.dact; p.out = dev_out;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-    p.Ho = conv_out(H, ksz, stride, pad); p.Wo = conv_out(W, ksz, stride, pad);
-    p.stride = stride; p.ksz = ksz; p.pad = pad; p.M = N * p.Ho * p.Wo; p.border_cls = border_cls;
-    p.splitk = 1; p.ksteps_per_split = ksz * ksz * (Cin / 64) + Cin2 / 64;
+    conv_geometry(p, N, H, W, Cin, Cout, ksz, stride, pad, Cin2);
+    p.border_cls = border_cls;
     p.post_relu = x.post_relu;
     if (Cin2) { p.in2 = x.in2; p.Cin2 = Cin2; p.in2_compact = x.in2_compact ? 1 : 0; }
     p.ablate = g_ablate; p.stamps = g_stamps;
     // fine: 1 / 0 force the 64- / 128-channel form of the linear-tile kernel, < 0 chooses as alink_embed does
     if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
+    DeviceAllocs mem;             // this call's: freed on every return
     void *d_wp = nullptr, *d_zero = nullptr, *d_slabs = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_wp); (void)hipFree(d_zero); (void)hipFree(d_slabs); };
-#define EX_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call, __FILE__, __LINE__); } } while (0)
-    EX_TRY(hipMalloc(&d_wp, hp.size() * 2));
-    EX_TRY(hipMalloc(&d_zero, 4096));
-    if (x.splitk > 1) EX_TRY(hipMalloc(&d_slabs, (size_t)x.splitk * p.M * Cout * 4));
-    EX_TRY(hipMemcpy(d_wp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
-    EX_TRY(hipMemset(d_zero, 0, 4096));
+    if ((rc = mem.upload(hp, &d_wp)) || (rc = mem.zeros(4096, &d_zero))) return rc;
+    if (x.splitk > 1 && (rc = mem.alloc((size_t)x.splitk * p.M * Cout * 4, &d_slabs))) return rc;
     p.wgt = d_wp; p.zero = d_zero;
-    hipError_t e = launch_conv_maybe_split(kernel, dtype, p, x.splitk, (float*)d_slabs, x, st);
+    hipError_t e = launch_conv_reported(kernel, dtype, p, x.splitk, (float*)d_slabs, x, st);
     hipError_t e2 = hipStreamSynchronize(st);
-#undef EX_TRY
-    cleanup();
     if (e != hipSuccess) return hip_fail(e, "launch_conv", __FILE__, __LINE__);
     if (e2 != hipSuccess) return hip_fail(e2, "hipStreamSynchronize", __FILE__, __LINE__);
     return ALINK_OK;
@@ -1508,7 +1353,6 @@ static int conv_nhwc_x2_impl(const float* dev_in, const float* dev_w, const floa
     ALINK_HIP(hipStreamSynchronize(st));
     const int K = ksz * ksz * Cin, Ho = conv_out(H, ksz, stride, pad), Wo = conv_out(W, ksz, stride, pad);
     const size_t Min = (size_t)N * H * W, M = (size_t)N * Ho * Wo;
-    const WeightLayout wl = weight_layout(kernel, ksz, Cin, true);
     auto pack_act = [&](const float* dev, size_t rows, int C, int e, std::vector<uint16_t>& q) -> int {
         std::vector<float> h(rows * C);
         ALINK_HIP(hipMemcpy(h.data(), dev, h.size() * 4, hipMemcpyDeviceToHost));
@@ -1520,48 +1364,35 @@ static int conv_nhwc_x2_impl(const float* dev_in, const float* dev_w, const floa
             }
         return ALINK_OK;
     };
-    std::vector<uint16_t> qin, qres, qw((size_t)Cout * K * 2);
+    std::vector<uint16_t> qin, qres, qw;
     if ((rc = pack_act(dev_in, Min, Cin, e_in, qin))) return rc;
     if (dev_resid && (rc = pack_act(dev_resid, M, Cout, e_res, qres))) return rc;
     {
         std::vector<float> h((size_t)Cout * K);
         ALINK_HIP(hipMemcpy(h.data(), dev_w, h.size() * 4, hipMemcpyDeviceToHost));
-        for (int co = 0; co < Cout; ++co)
-            for (int tap = 0; tap < ksz * ksz; ++tap)
-                for (int ci = 0; ci < Cin; ++ci) {
-                    const size_t at = wl.at(co, tap, ci);
-                    split16(std::ldexp((double)h[(size_t)co * K + (size_t)tap * Cin + ci], e_w), &qw[at], &qw[at + wl.lo_offset()]);
-                }
+        qw = pack_conv_weights(weight_layout(kernel, ksz, Cin, true), ALINK_DT_F16X2, Round16::Direct, Cout,
+                               [&](int co, int tap, int ci) { return (double)h[(size_t)co * K + (size_t)tap * Cin + ci]; },
+                               [](int, int) { return 0.0; }, &e_w).w;
     }
+    DeviceAllocs mem;             // this call's: freed on every return
     void *d_in = nullptr, *d_res = nullptr, *d_w = nullptr, *d_out = nullptr, *d_zero = nullptr, *d_slabs = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_in); (void)hipFree(d_res); (void)hipFree(d_w); (void)hipFree(d_out); (void)hipFree(d_zero); (void)hipFree(d_slabs); };
-#define X2_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(e__, #call, __FILE__, __LINE__); } } while (0)
-    X2_TRY(hipMalloc(&d_in, qin.size() * 2));
-    X2_TRY(hipMalloc(&d_w, qw.size() * 2));
-    X2_TRY(hipMalloc(&d_out, M * Cout * 4));
-    X2_TRY(hipMalloc(&d_zero, 4096));
-    if (x.splitk > 1) X2_TRY(hipMalloc(&d_slabs, (size_t)x.splitk * M * Cout * 4));
-    X2_TRY(hipMemcpy(d_in, qin.data(), qin.size() * 2, hipMemcpyHostToDevice));
-    X2_TRY(hipMemcpy(d_w, qw.data(), qw.size() * 2, hipMemcpyHostToDevice));
-    X2_TRY(hipMemset(d_zero, 0, 4096));
-    if (dev_resid) {
-        X2_TRY(hipMalloc(&d_res, qres.size() * 2));
-        X2_TRY(hipMemcpy(d_res, qres.data(), qres.size() * 2, hipMemcpyHostToDevice));
-    }
+    if ((rc = mem.upload(qin, &d_in)) || (rc = mem.upload(qw, &d_w)) || (rc = mem.alloc(M * Cout * 4, &d_out)) ||
+        (rc = mem.zeros(4096, &d_zero))) return rc;
+    if (x.splitk > 1 && (rc = mem.alloc((size_t)x.splitk * M * Cout * 4, &d_slabs))) return rc;
+    if (dev_resid && (rc = mem.upload(qres, &d_res))) return rc;
     ConvParams p{};
     p.in = d_in; p.wgt = d_w; p.bias = dev_bias; p.alpha = dev_alpha; p.resid = d_res; p.out = d_out;
-    p.zero = d_zero; p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.Ho = Ho; p.Wo = Wo;
-    p.stride = stride; p.ksz = ksz; p.pad = pad; p.M = (int)M; p.border_cls = border_cls;
-    p.splitk = 1; p.ksteps_per_split = 3 * ksz * ksz * (Cin / 64);
+    p.zero = d_zero; p.border_cls = border_cls;
+    conv_geometry(p, N, H, W, Cin, Cout, ksz, stride, pad, 0, true);
     p.post_relu = x.post_relu; p.nprod = x.nprod;
     p.acc_scale = std::ldexp(1.f, e_out - e_in - e_w);
     p.bias_scale = std::ldexp(1.f, e_out);
     p.res_scale = std::ldexp(1.f, e_out - e_res);
     if (traits(kernel).fine) p.fine = fine < 0 ? fine_form(kernel, p.M, Cout) : (fine ? 1 : 0);
-    X2_TRY(launch_conv_maybe_split(kernel, ALINK_DT_F16X2, p, x.splitk, (float*)d_slabs, x, st));
-    X2_TRY(hipStreamSynchronize(st));
+    ALINK_HIP(launch_conv_reported(kernel, ALINK_DT_F16X2, p, x.splitk, (float*)d_slabs, x, st));
+    ALINK_HIP(hipStreamSynchronize(st));
     std::vector<uint16_t> qo(M * Cout * 2);
-    X2_TRY(hipMemcpy(qo.data(), d_out, qo.size() * 2, hipMemcpyDeviceToHost));
+    ALINK_HIP(hipMemcpy(qo.data(), d_out, qo.size() * 2, hipMemcpyDeviceToHost));
     std::vector<float> ho(M * Cout);
     for (size_t m = 0; m < M; ++m)
         for (int c = 0; c < Cout; ++c) {
@@ -1571,9 +1402,7 @@ static int conv_nhwc_x2_impl(const float* dev_in, const float* dev_w, const floa
             memcpy(&ll, &qo[at + 64], 2);
             ho[m * Cout + c] = (float)std::ldexp((double)hh + (double)ll, -e_out);
         }
-    X2_TRY(hipMemcpy(dev_out, ho.data(), ho.size() * 4, hipMemcpyHostToDevice));
-#undef X2_TRY
-    cleanup();
+    ALINK_HIP(hipMemcpy(dev_out, ho.data(), ho.size() * 4, hipMemcpyHostToDevice));
     return ALINK_OK;
 }
 

@@ -16,6 +16,7 @@
 // normalisation exactly as in the symbol and no border classes are needed; PReLU and the residual add are the GEMM
 // epilogue.  Layer order and tensor names: backbone.hip (insightface LResNet-E-IR).
 #include "alink_common.h"
+#include "net_host.h"
 #include "sgemm.h"
 
 #include <cmath>
@@ -83,20 +84,13 @@ struct F32Net {
     float *d_fc_w = nullptr, *d_fc_bias = nullptr;      // [K][emb] (k = pos * C + ch), folded bias
     int fcK = 0, emb = 0, H = 0, W = 0, last_buf = 0;
     int wide0 = 64;                                     // max(widths[0], widths[1]): channels of the widest full-resolution tensor
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
     std::string err;
-    ~F32Net() {
-        for (void* p : allocs) (void)hipFree(p);
-    }
 };
 
 namespace {
 
-bool up(F32Net* n, const std::vector<float>& h, float** d) {
-    if (hipMalloc((void**)d, h.size() * sizeof(float)) != hipSuccess) return false;
-    n->allocs.push_back(*d);
-    return hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-}
+bool up(F32Net* n, const std::vector<float>& h, float** d) { return n->mem.upload(h, (void**)d) == ALINK_OK; }
 
 // B[(ky*ks + kx)*Cin + ci][co] = post.a[co] * w[co][ci][ky][kx] (w: MXNet O,I,kh,kw), bias = post.b
 bool conv_layer(F32Net* n, F32Layer& L, const std::vector<float>& w, const Affine& post, const std::vector<float>* prelu) {

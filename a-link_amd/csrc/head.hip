@@ -20,6 +20,7 @@
 //   to binary_accuracy = mean(round(p) == y) (round half to even), not weighted;
 //   Adadelta: a = rho*a + (1-rho)*g^2; u = g*sqrt(d+eps)/sqrt(a+eps); p -= lr*u; d = rho*d+(1-rho)*u^2.
 #include "alink_common.h"
+#include "net_host.h"
 
 #include <algorithm>
 #include <vector>
@@ -58,7 +59,7 @@ struct alink_head {
     float* d_tiny = nullptr;     // per-row-group partials of the tiny-batch train step
     float* d_mini = nullptr;     // Dense1 partial sums of SmallRes' three-launch step ([D / 32][n][128]); only for that head shape
     unsigned* d_counter = nullptr;   // row groups finished (tiny_eval), 0 between launches
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
     // hipGraph cache of the fine-tune step (a launch-bound chain of 8-9 small kernels): one executable
     // graph per distinct (operand pointers, n, grad_scale, apply); replayed while the caller keeps
     // feeding the same buffers (DenseHead stages every batch into persistent tensors for that purpose)
@@ -73,7 +74,6 @@ struct alink_head {
                                 // bound by kernel-to-kernel dependency latency, not by launch cost; kept as an option
     ~alink_head() {
         for (auto& g : graphs) (void)hipGraphExecDestroy(g.exec);
-        for (void* p : allocs) (void)hipFree(p);
     }
 };
 
@@ -830,10 +830,7 @@ __global__ void adadelta_two_kernel(float* __restrict__ p2, const float* __restr
 inline dim3 g1(long long n) { return dim3((unsigned)((n + 255) / 256), 1, 1); }
 
 int head_alloc(alink_head* h, float** p, size_t count) {
-    ALINK_HIP(hipMalloc((void**)p, count * sizeof(float)));
-    h->allocs.push_back(*p);
-    ALINK_HIP(hipMemset(*p, 0, count * sizeof(float)));
-    return ALINK_OK;
+    return h->mem.zeros(count * sizeof(float), (void**)p);
 }
 
 // bf16 mode: bring the bf16 copy (and, if asked, its widened image) up to date with the f32 master parameters
@@ -2249,7 +2246,7 @@ int alink_head_set_compute_dtype(alink_head_t* h, int dtype) {
             return hip_fail(e, "hipMalloc (bf16 compute mode buffers)", __FILE__, __LINE__);
         }
         h->d_pq = (decltype(h->d_pq))pq; h->d_pqf = (decltype(h->d_pqf))pqf; h->d_wt = (decltype(h->d_wt))wt;
-        h->allocs.push_back(pq); h->allocs.push_back(pqf); h->allocs.push_back(wt);
+        h->mem.adopt(pq); h->mem.adopt(pqf); h->mem.adopt(wt);
     }
     h->qmode = dtype == ALINK_DT_BF16 ? 1 : 0;
     h->packed_dirty = h->pq_dirty = h->pqf_dirty = true;

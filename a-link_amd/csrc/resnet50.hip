@@ -21,6 +21,7 @@
 // Input gradients (FGSM / PGD extension; 16-bit modes): alink_resnet50_enable_grad .. alink_resnet50_input_grad at the end of
 // this file walk the units backwards on the same convolution kernels; the kernels without a forward twin are in resnet50_bwd.hip.
 #include "conv_device.h"
+#include "net_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -327,19 +328,6 @@ __global__ void avgpool_x2_kernel(const _Float16* __restrict__ in, float* __rest
     if (bad && nonfinite) *nonfinite = 1;
 }
 
-static inline void split16(double x, uint16_t* hi, uint16_t* lo) {
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (double)h);
-    memcpy(hi, &h, 2);
-    memcpy(lo, &l, 2);
-}
-static inline int scale_exp(double maxabs) {       // maxabs * 2^e in [1024, 2048)
-    if (!(maxabs > 0.0) || !std::isfinite(maxabs)) return 0;
-    return 10 - std::ilogb(maxabs);
-}
-
-uint16_t cvt(int dtype, float f) { return dtype == ALINK_DT_BF16 ? f32_to_bf16_rne(f) : f32_to_f16_rne(f); }
-
 struct Op {
     int kind;             // 0 stem7, 1 maxpool, 2 conv, 3 avgpool
     ConvParams cp;        // kind 2: everything but the per-call pointers/N/M
@@ -370,9 +358,9 @@ struct alink_resnet50 {
     int device = -1;
     int H, W, dtype;
     float eps;
-    std::vector<std::pair<std::string, size_t>> expected;
-    std::map<std::string, std::vector<float>> raw;
+    TensorTable tensors;
     bool finalized = false;
+    DeviceAllocs mem;
     std::vector<Op> ops;
     void* d_stem_w = nullptr;
     float* d_stem_bias = nullptr;
@@ -380,20 +368,13 @@ struct alink_resnet50 {
     float* d_zero_alpha = nullptr;       // 2048 zeros: PReLU slope 0 == ReLU
     int Ho1, Wo1, Hp, Wp, Hf, Wf;
     size_t buf_elems_per_image = 0;
-    // split precision
-    bool calibrated = false;
+    // split precision; cal.h_flag / d_flag: the pinned word the average-pool kernel raises on a non-finite feature
+    ScaleCalibration cal;
     int stem_e_w = 0;
-    unsigned* d_absmax = nullptr;
-    int *h_flag = nullptr, *d_flag = nullptr;      // pinned word the average-pool kernel raises on a non-finite feature
     // input-gradient support
     bool grad = false;
     void* d_stem_wfrag = nullptr;        // folded stem weights by tap, as the matrix-core fragments of the stem backward
     std::vector<size_t> slot_elems;      // per image, per cache slot
-    std::vector<void*> allocs;
-    ~alink_resnet50() {
-        for (void* p : allocs) (void)hipFree(p);
-        if (h_flag) (void)hipHostFree(h_flag);
-    }
 };
 
 namespace {
@@ -404,24 +385,16 @@ const int kMid[4] = {64, 128, 256, 512};
 int same_out(int x, int s) { return (x + s - 1) / s; }
 
 void expect_conv(alink_resnet50* r, const std::string& n, int kh, int cin, int cout) {
-    r->expected.emplace_back(n + "/kernel", (size_t)kh * kh * cin * cout);
+    r->tensors.expect(n + "/kernel", (size_t)kh * kh * cin * cout);
     for (const char* s : {"/bn/gamma", "/bn/beta", "/bn/moving_mean", "/bn/moving_variance"})
-        r->expected.emplace_back(n + s, (size_t)cout);
-}
-
-template <typename V>
-int upload(alink_resnet50* r, const std::vector<V>& h, void** d) {
-    ALINK_HIP(hipMalloc(d, h.size() * sizeof(V)));
-    r->allocs.push_back(*d);
-    ALINK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(V), hipMemcpyHostToDevice));
-    return ALINK_OK;
+        r->tensors.expect(n + s, (size_t)cout);
 }
 
 void bn_fold(const alink_resnet50* r, const std::string& n, std::vector<double>& a, std::vector<double>& b) {
-    const auto& g = r->raw.at(n + "/bn/gamma");
-    const auto& be = r->raw.at(n + "/bn/beta");
-    const auto& mu = r->raw.at(n + "/bn/moving_mean");
-    const auto& var = r->raw.at(n + "/bn/moving_variance");
+    const auto& g = r->tensors.at(n + "/bn/gamma");
+    const auto& be = r->tensors.at(n + "/bn/beta");
+    const auto& mu = r->tensors.at(n + "/bn/moving_mean");
+    const auto& var = r->tensors.at(n + "/bn/moving_variance");
     a.resize(g.size());
     b.resize(g.size());
     for (size_t i = 0; i < g.size(); ++i) {
@@ -433,7 +406,7 @@ void bn_fold(const alink_resnet50* r, const std::string& n, std::vector<double>&
 // Keras kernel (kh, kw, in, out) + following BN -> permuted T rows + f32 bias; appends a conv op
 int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int cin, int cout, int Hin, int Win,
              int in_buf, int out_buf, int resid_buf, bool relu, bool post_relu, int unit, int role) {
-    const auto& w = r->raw.at(name + "/kernel");
+    const auto& w = r->tensors.at(name + "/kernel");
     std::vector<double> a, b;
     bn_fold(r, name, a, b);
     const int pad = k == 3 ? 1 : 0;
@@ -443,50 +416,28 @@ int add_conv(alink_resnet50* r, const std::string& name, int k, int stride, int 
     op.name = name;
     const bool x2 = r->dtype == ALINK_DT_F16X2;
     op.kernel = x2 ? linear_variant_x2(k, stride, pad, Hin, Win, cin, cout) : direct_variant_tiles(k, stride, pad, Hin, Win, cin, cout);
-    const WeightLayout wl = weight_layout(op.kernel, k, cin, x2);
-    const int K = k * k * cin;
-    std::vector<uint16_t> wq(wl.size(cout));
-    if (x2) {
-        double mx = 0.0;
-        for (int co = 0; co < cout; ++co)
-            for (size_t i = 0; i < (size_t)K; ++i) mx = std::max(mx, std::fabs(a[co] * (double)w[i * cout + co]));
-        op.e_w = scale_exp(mx);
-    }
-    for (int co = 0; co < cout; ++co)
-        for (int tap = 0; tap < k * k; ++tap)
-            for (int ci = 0; ci < cin; ++ci) {
-                const double v = a[co] * (double)w[((size_t)tap * cin + ci) * cout + co];
-                const size_t at = wl.at(co, tap, ci);
-                if (x2) split16(std::ldexp(v, op.e_w), &wq[at], &wq[at + wl.lo_offset()]);
-                else    wq[at] = cvt(r->dtype, (float)v);
-            }
+    auto folded = [&](int co, int tap, int ci) { return a[co] * (double)w[((size_t)tap * cin + ci) * cout + co]; };
+    const PackedWeights wq = pack_conv_weights(weight_layout(op.kernel, k, cin, x2), r->dtype, Round16::ViaFloat32, cout, folded);
+    op.e_w = wq.e_w;
     std::vector<float> bias(cout);
     for (int co = 0; co < cout; ++co) bias[co] = (float)b[co];
     void* d_w = nullptr;
     float* d_b = nullptr;
     int rc;
-    if ((rc = upload(r, wq, &d_w))) return rc;
-    if ((rc = upload(r, bias, (void**)&d_b))) return rc;
+    if ((rc = r->mem.upload(wq.w, &d_w))) return rc;
+    if ((rc = r->mem.upload(bias, (void**)&d_b))) return rc;
     ConvParams& p = op.cp;
     memset(&p, 0, sizeof(p));
     p.wgt = d_w; p.bias = d_b; p.alpha = relu ? r->d_zero_alpha : nullptr; p.zero = r->d_zero;
-    p.H = Hin; p.W = Win; p.Cin = cin; p.Cout = cout; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.ksz = k; p.pad = pad;
-    p.border_cls = 0; p.splitk = 1; p.ksteps_per_split = k * k * (cin / 64) * (x2 ? 3 : 1); p.post_relu = post_relu ? 1 : 0;
+    conv_geometry(p, 0, Hin, Win, cin, cout, k, stride, pad, 0, x2);       // N, M: with_batch, per call
+    p.post_relu = post_relu ? 1 : 0;
     op.in_buf = in_buf; op.out_buf = out_buf; op.resid_buf = resid_buf;
     op.unit = unit; op.role = role;
     if (r->grad) {
         // d(input) = conv(d(output), Wb) at stride 1 on the OUTPUT grid: Wb[ci][tap'][co] = Wfolded[co][k*k-1-tap'][ci], the
         // values the forward multiplies by.  (A stride-2 1x1 reads only even positions: its result is scattered there.)
         op.bkernel = direct_variant_tiles(k, 1, pad, Ho, Wo, cout, cin);
-        const WeightLayout bl = weight_layout(op.bkernel, k, cout);
-        std::vector<uint16_t> wb(bl.size(cin));
-        for (int ci = 0; ci < cin; ++ci)
-            for (int tap = 0; tap < k * k; ++tap) {
-                const int ft = k * k - 1 - tap;
-                for (int co = 0; co < cout; ++co)
-                    wb[bl.at(ci, tap, co)] = cvt(r->dtype, (float)(a[co] * (double)w[((size_t)ft * cin + ci) * cout + co]));
-            }
-        if ((rc = upload(r, wb, &op.d_wb))) return rc;
+        if ((rc = r->mem.upload(pack_conv_weights_backward(weight_layout(op.bkernel, k, cout), r->dtype, Round16::ViaFloat32, cin, folded), &op.d_wb))) return rc;
         if (role != 4) {                                   // the projection's output is not needed again
             op.slot = (int)r->slot_elems.size();
             r->slot_elems.push_back((size_t)Ho * Wo * cout);
@@ -545,54 +496,33 @@ void alink_resnet50_destroy(alink_resnet50_t* r) {
     DeviceGuard dg(r->device);
     delete r;
 }
-int alink_resnet50_num_tensors(const alink_resnet50_t* r) { return r ? (int)r->expected.size() : 0; }
+int alink_resnet50_num_tensors(const alink_resnet50_t* r) { return r ? r->tensors.count() : 0; }
 int alink_resnet50_tensor_info(const alink_resnet50_t* r, int i, const char** name, size_t* count) {
-    ALINK_REQUIRE(r && i >= 0 && i < (int)r->expected.size(), ALINK_EINVAL, "tensor index out of range");
-    if (name) *name = r->expected[i].first.c_str();
-    if (count) *count = r->expected[i].second;
-    return ALINK_OK;
+    ALINK_REQUIRE(r, ALINK_EINVAL, "tensor index out of range");
+    return r->tensors.info(i, name, count);
 }
 
 int alink_resnet50_load(alink_resnet50_t* r, const char* name, const float* host, size_t count) {
-    ALINK_REQUIRE(r && name && host, ALINK_EINVAL, "NULL argument");
-    ALINK_REQUIRE(!r->finalized, ALINK_ESTATE, "network already finalized");
-    for (const auto& e : r->expected)
-        if (e.first == name) {
-            ALINK_REQUIRE(e.second == count, ALINK_EINVAL, "tensor %s: expected %zu elements, got %zu", name, e.second, count);
-            r->raw[name].assign(host, host + count);
-            return ALINK_OK;
-        }
-    set_error("tensor %s is not part of the VGGFace2 ResNet-50", name);
-    return ALINK_ENOTFOUND;
+    ALINK_REQUIRE(r, ALINK_EINVAL, "NULL argument");
+    return r->tensors.load(name, host, count, r->finalized, "the VGGFace2 ResNet-50");
 }
 
 int alink_resnet50_finalize(alink_resnet50_t* r) {
     ALINK_REQUIRE(r && !r->finalized, ALINK_ESTATE, "bad state");
     DeviceGuard dg(r->device);
-    for (const auto& e : r->expected)
-        ALINK_REQUIRE(r->raw.count(e.first), ALINK_ESTATE, "tensor %s was never loaded", e.first.c_str());
-    int rc = init_kernels();
+    int rc = r->tensors.require_all_loaded();
     if (rc) return rc;
+    if ((rc = init_kernels())) return rc;
     ALINK_HIP(hipFuncSetAttribute((const void*)stem7_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     ALINK_HIP(hipFuncSetAttribute((const void*)stem7_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     const bool x2 = r->dtype == ALINK_DT_F16X2;
     ALINK_HIP(hipFuncSetAttribute((const void*)stem7_x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    ALINK_HIP(hipHostMalloc((void**)&r->h_flag, 64, hipHostMallocMapped));
-    *r->h_flag = 0;
-    ALINK_HIP(hipHostGetDevicePointer((void**)&r->d_flag, r->h_flag, 0));
-    if (x2) {
-        ALINK_HIP(hipMalloc((void**)&r->d_absmax, 256));
-        r->allocs.push_back(r->d_absmax);
-    }
-    ALINK_HIP(hipMalloc(&r->d_zero, 4096));
-    r->allocs.push_back(r->d_zero);
-    ALINK_HIP(hipMemset(r->d_zero, 0, 4096));
-    ALINK_HIP(hipMalloc((void**)&r->d_zero_alpha, 2048 * 4));
-    r->allocs.push_back(r->d_zero_alpha);
-    ALINK_HIP(hipMemset(r->d_zero_alpha, 0, 2048 * 4));
+    if ((rc = r->cal.init(r->mem, x2))) return rc;
+    if ((rc = r->mem.zeros(4096, &r->d_zero))) return rc;
+    if ((rc = r->mem.zeros(2048 * 4, (void**)&r->d_zero_alpha))) return rc;
     // ---- stem weights [64'][192], k = ky*24 + kx*3 + c
     {
-        const auto& w = r->raw.at("conv1/7x7_s2/kernel");     // (7, 7, 3, 64)
+        const auto& w = r->tensors.at("conv1/7x7_s2/kernel");     // (7, 7, 3, 64)
         std::vector<double> a, b;
         bn_fold(r, "conv1/7x7_s2", a, b);
         std::vector<uint16_t> wq((size_t)64 * 192 * (x2 ? 2 : 1), x2 ? (uint16_t)0 : cvt(r->dtype, 0.f));
@@ -614,11 +544,11 @@ int alink_resnet50_finalize(alink_resnet50_t* r) {
                     }
         std::vector<float> bias(64);
         for (int co = 0; co < 64; ++co) bias[co] = (float)b[co];
-        if ((rc = upload(r, wq, &r->d_stem_w))) return rc;
-        if ((rc = upload(r, bias, (void**)&r->d_stem_bias))) return rc;
+        if ((rc = r->mem.upload(wq, &r->d_stem_w))) return rc;
+        if ((rc = r->mem.upload(bias, (void**)&r->d_stem_bias))) return rc;
     }
     if (r->grad) {
-        const auto& w = r->raw.at("conv1/7x7_s2/kernel");
+        const auto& w = r->tensors.at("conv1/7x7_s2/kernel");
         std::vector<double> a, b;
         bn_fold(r, "conv1/7x7_s2", a, b);
         // the stem backward's A fragments [tap][channel half][lane = (q, row c)][8] (resnet50_bwd.hip): row c < 3 holds the folded
@@ -633,7 +563,7 @@ int alink_resnet50_finalize(alink_resnet50_t* r) {
                             const double v = a[co] * (double)w[((size_t)tap * 3 + c) * 64 + co];
                             wf[((((size_t)tap * 2 + h) * 64) + 16 * q + c) * 8 + i] = cvt(r->dtype, (float)v);
                         }
-        if ((rc = upload(r, wf, &r->d_stem_wfrag))) return rc;
+        if ((rc = r->mem.upload(wf, &r->d_stem_wfrag))) return rc;
     }
     r->buf_elems_per_image = (size_t)r->Ho1 * r->Wo1 * 64;
     // ---- op list.  Buffers 0..3; stem -> 0, pool -> 1 (= x)
@@ -666,7 +596,7 @@ int alink_resnet50_finalize(alink_resnet50_t* r) {
         }
     }
     Op ap; ap.kind = 3; ap.in_buf = x; ap.name = "avg_pool"; r->ops.push_back(ap);
-    r->raw.clear();
+    r->tensors.clear();
     r->finalized = true;
     return ALINK_OK;
 }
@@ -677,8 +607,6 @@ size_t alink_resnet50_workspace_bytes(const alink_resnet50_t* r, int n_images) {
     return 4 * one;
 }
 
-// calib (split precision only): 0 = a forward; 1 = choose every tensor's scale exponent from this batch; 2 = the same, never
-// above the exponents already held.  Synchronous when != 0.  (The scheme is csrc/backbone.hip's: embed_impl, settle.)
 static void r50_grad_layout(const alink_resnet50* r, int n, R50GradLayout* L) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t o = 0;
@@ -691,6 +619,8 @@ static void r50_grad_layout(const alink_resnet50* r, int n, R50GradLayout* L) {
     L->total = o;
 }
 
+// calib (split precision only): 0 = a forward; 1 = choose every tensor's scale exponent from this batch; 2 = the same, never
+// above the exponents already held.  Synchronous when != 0.  (ScaleCalibration::settle.)
 // GL != nullptr: the cached forward — the same launches, every kept output written to its own slot of the activation cache
 // instead of one of the four rotating buffers (the kernels see other addresses, nothing else: bit-identical results)
 static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
@@ -703,45 +633,15 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
     const bool x2 = r->dtype == ALINK_DT_F16X2;
     ALINK_REQUIRE((long long)n * r->buf_elems_per_image * (x2 ? 2 : 1) < (1ll << 31), ALINK_EINVAL, "batch of %d too large; split it", n);
     ALINK_REQUIRE(!calib || x2, ALINK_ESTATE, "only the split-precision mode is calibrated");
-    ALINK_REQUIRE(!x2 || calib || r->calibrated, ALINK_ESTATE, "split-precision network: alink_resnet50_calibrate has not run");
+    ALINK_REQUIRE(!x2 || calib || r->cal.calibrated, ALINK_ESTATE, "split-precision network: alink_resnet50_calibrate has not run");
     const size_t one = ((size_t)n * r->buf_elems_per_image * (x2 ? 4 : 2) + 255) & ~(size_t)255;
     int bexp[4] = {0, 0, 0, 0};
-    auto settle = [&](int* e_io, const void* out, size_t n_elems, auto&& launch) -> int {
-        int e = *e_io;
-        for (int attempt = 0; attempt < 24; ++attempt) {
-            const int rcl = launch(e);
-            if (rcl) return rcl;
-            if (!calib) break;
-            unsigned bits = 0;
-            ALINK_HIP(hipMemsetAsync(r->d_absmax, 0, 4, st));
-            ALINK_HIP(launch_absmax_f16(out, n_elems, r->d_absmax, st));
-            ALINK_HIP(hipMemcpyAsync(&bits, r->d_absmax, 4, hipMemcpyDeviceToHost, st));
-            ALINK_HIP(hipStreamSynchronize(st));
-            float m;
-            memcpy(&m, &bits, 4);
-            if (bits >= 0x7f800000u) { e -= 8; continue; }
-            if (m == 0.f) break;
-            int want = e + (10 - std::ilogb(m));
-            if (calib == 2 && r->calibrated) want = std::min(want, *e_io);
-            if (want == e) break;
-            e = want;
-        }
-        *e_io = e;
-        return ALINK_OK;
-    };
     void* bptr[4];
     for (int i = 0; i < 4; ++i) bptr[i] = GL ? nullptr : (void*)((char*)ws + one * i);
     auto buf = [&](int id) -> void* { return bptr[id]; };
     const bool prof = ms != nullptr;
-    std::vector<hipEvent_t> ev;
-    auto mark = [&]() -> int {
-        if (!prof) return ALINK_OK;
-        hipEvent_t e;
-        ALINK_HIP(hipEventCreate(&e));
-        ALINK_HIP(hipEventRecord(e, st));
-        ev.push_back(e);
-        return ALINK_OK;
-    };
+    LaunchTimer timer(prof);
+    auto mark = [&]() -> int { return timer.mark(st); };
     int rc, k = 0;
     if ((rc = mark())) return rc;
     for (Op& op : r->ops) {
@@ -761,7 +661,7 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
             ALINK_REQUIRE(lds <= 64 * 1024, ALINK_EINVAL, "image too wide for the stem band (%zu B of LDS)", lds);
             dim3 grid((p.Ho + S7_ROWS - 1) / S7_ROWS, n);
             if (x2) {
-                rc = settle(&op.e_out, p.out, (size_t)n * p.Ho * p.Wo * 128, [&](int e) -> int {
+                rc = r->cal.settle(calib, &op.e_out, p.out, (size_t)n * p.Ho * p.Wo * 128, st, [&](int e) -> int {
                     // the loader stores (pixel - mean) x 2^6: |.| < 2^14
                     hipLaunchKernelGGL(stem7_x2_kernel, grid, dim3(256), lds, st, p, std::ldexp(1.f, e - 6 - r->stem_e_w), std::ldexp(1.f, e));
                     ALINK_HIP(hipGetLastError());
@@ -790,9 +690,9 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
         } else if (op.kind == 2) {
             ConvParams p = op.cp;
             p.in = buf(op.in_buf); p.out = buf(op.out_buf); p.resid = op.resid_buf >= 0 ? buf(op.resid_buf) : nullptr;
-            p.N = n; p.M = n * p.Ho * p.Wo;
+            with_batch(p, n);
             if (x2) {
-                rc = settle(&op.e_out, p.out, (size_t)p.M * p.Cout * 2, [&](int e) -> int {
+                rc = r->cal.settle(calib, &op.e_out, p.out, (size_t)p.M * p.Cout * 2, st, [&](int e) -> int {
                     p.acc_scale = std::ldexp(1.f, e - bexp[op.in_buf] - op.e_w);
                     p.bias_scale = std::ldexp(1.f, e);
                     p.res_scale = op.resid_buf >= 0 ? std::ldexp(1.f, e - bexp[op.resid_buf]) : 1.f;
@@ -808,14 +708,14 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
             const int tot = n * 2048 / 8;
             if (x2)
                 hipLaunchKernelGGL(avgpool_x2_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, (const _Float16*)buf(op.in_buf),
-                                   dev_out, n, r->Hf * r->Wf, 2048, std::ldexp(1.f, -bexp[op.in_buf]), r->d_flag);
+                                   dev_out, n, r->Hf * r->Wf, 2048, std::ldexp(1.f, -bexp[op.in_buf]), r->cal.d_flag);
             else
             if (r->dtype == ALINK_DT_BF16)
                 hipLaunchKernelGGL(avgpool_kernel<__bf16>, dim3((tot + 255) / 256), dim3(256), 0, st,
-                                   (const __bf16*)buf(op.in_buf), dev_out, n, r->Hf * r->Wf, 2048, r->d_flag);
+                                   (const __bf16*)buf(op.in_buf), dev_out, n, r->Hf * r->Wf, 2048, r->cal.d_flag);
             else
                 hipLaunchKernelGGL(avgpool_kernel<_Float16>, dim3((tot + 255) / 256), dim3(256), 0, st,
-                                   (const _Float16*)buf(op.in_buf), dev_out, n, r->Hf * r->Wf, 2048, r->d_flag);
+                                   (const _Float16*)buf(op.in_buf), dev_out, n, r->Hf * r->Wf, 2048, r->cal.d_flag);
         }
         ALINK_HIP(hipGetLastError());
         if (prof && k < *n_ops) flops[k] = fl;
@@ -824,18 +724,13 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
     }
     if (prof) {
         ALINK_HIP(hipStreamSynchronize(st));
-        for (int i = 0; i + 1 < (int)ev.size() && i < *n_ops; ++i) {
-            float t = 0.f;
-            ALINK_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            ms[i] = t;
-        }
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        if ((rc = timer.elapsed(ms, *n_ops))) return rc;
         *n_ops = k;
     }
     if (calib) {
         ALINK_HIP(hipStreamSynchronize(st));
-        ALINK_REQUIRE(*r->h_flag == 0, ALINK_EINVAL, "calibration batch produced non-finite features");
-        r->calibrated = true;
+        ALINK_REQUIRE(*r->cal.h_flag == 0, ALINK_EINVAL, "calibration batch produced non-finite features");
+        r->cal.calibrated = true;
     }
     return ALINK_OK;
 }
@@ -848,9 +743,7 @@ int alink_resnet50_calibrate(alink_resnet50_t* r, const float* dev_in, int n_ima
     DeviceGuard dg(r->device);
     hipStream_t st = (hipStream_t)stream;
     ALINK_HIP(hipStreamSynchronize(st));
-    const int pending = *(volatile int*)r->h_flag;          // a report not read yet survives the calibration run
-    struct Keep { int* f; int v; ~Keep() { if (v) *(volatile int*)f = 1; } } keep{r->h_flag, pending};
-    *r->h_flag = 0;
+    ScaleCalibration::PendingReport keep(r->cal);            // a report not read yet survives the calibration run
     float* scratch = nullptr;
     ALINK_HIP(hipMalloc((void**)&scratch, (size_t)n_images * 2048 * sizeof(float)));
     const int rc = r50_run(r, dev_in, n_images, preprocessed, scratch, dev_workspace, workspace_bytes, st, nullptr, nullptr, nullptr,
@@ -866,29 +759,17 @@ int alink_resnet50_num_scales(const alink_resnet50_t* r) {
 
 int alink_resnet50_get_scales(const alink_resnet50_t* r, int* exponents, int n) {
     ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_resnet50_get_scales before finalize");
-    ALINK_REQUIRE(r->dtype == ALINK_DT_F16X2, ALINK_ESTATE, "only the split-precision mode (ALINK_DT_F16X2) has scales");
-    ALINK_REQUIRE(r->calibrated, ALINK_ESTATE, "alink_resnet50_get_scales before alink_resnet50_calibrate / set_scales");
-    ALINK_REQUIRE(exponents && n == (int)r->ops.size(), ALINK_EINVAL, "expected room for %d exponents, got %d", (int)r->ops.size(), n);
-    for (size_t i = 0; i < r->ops.size(); ++i) exponents[i] = r->ops[i].e_out;
-    return ALINK_OK;
+    return r->cal.get_scales("resnet50", r->dtype == ALINK_DT_F16X2, (int)r->ops.size(), [r](int i) { return r->ops[i].e_out; }, exponents, n);
 }
 
 int alink_resnet50_set_scales(alink_resnet50_t* r, const int* exponents, int n) {
     ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_resnet50_set_scales before finalize");
-    ALINK_REQUIRE(r->dtype == ALINK_DT_F16X2, ALINK_ESTATE, "only the split-precision mode (ALINK_DT_F16X2) has scales");
-    ALINK_REQUIRE(exponents && n == (int)r->ops.size(), ALINK_EINVAL, "expected %d exponents, got %d", (int)r->ops.size(), n);
-    for (int i = 0; i < n; ++i)
-        ALINK_REQUIRE(exponents[i] >= -126 && exponents[i] <= 126, ALINK_EINVAL, "exponent %d of op %d is not a float32 power of two", exponents[i], i);
-    for (size_t i = 0; i < r->ops.size(); ++i) r->ops[i].e_out = exponents[i];
-    r->calibrated = true;
-    return ALINK_OK;
+    return r->cal.set_scales("op", r->dtype == ALINK_DT_F16X2, (int)r->ops.size(), [r](int i) -> int& { return r->ops[i].e_out; }, exponents, n);
 }
 
 int alink_resnet50_range_flag(alink_resnet50_t* r, int reset) {
     ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_resnet50_range_flag before finalize");
-    const int v = *(volatile int*)r->h_flag != 0 ? 1 : 0;
-    if (reset) *(volatile int*)r->h_flag = 0;
-    return v;
+    return r->cal.range_flag(reset);
 }
 
 int alink_resnet50_embed(alink_resnet50_t* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,
@@ -964,16 +845,8 @@ static int r50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_ima
                           void* dev_workspace, size_t workspace_bytes, void* stream, float* ms, int* n_stages) {
     ALINK_REQUIRE(r && r->finalized && r->grad, ALINK_ESTATE, "needs alink_resnet50_enable_grad + finalize");
     DeviceGuard dg(r->device);
-    std::vector<hipEvent_t> ev;
-    struct Drop { std::vector<hipEvent_t>& v; ~Drop() { for (hipEvent_t e : v) (void)hipEventDestroy(e); } } drop{ev};
-    auto mark = [&]() -> int {
-        if (!ms) return ALINK_OK;
-        hipEvent_t e;
-        ALINK_HIP(hipEventCreate(&e));
-        ev.push_back(e);
-        ALINK_HIP(hipEventRecord(e, (hipStream_t)stream));
-        return ALINK_OK;
-    };
+    LaunchTimer timer(ms != nullptr);
+    auto mark = [&]() -> int { return timer.mark((hipStream_t)stream); };
     const int N = n_images, dt = r->dtype;
     ALINK_REQUIRE(dev_dfeat && dev_dpix && dev_workspace && N > 0, ALINK_EINVAL, "bad argument");
     ALINK_REQUIRE(((uintptr_t)dev_workspace & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
@@ -1004,8 +877,7 @@ static int r50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_ima
         ConvParams p{};
         p.in = in; p.wgt = op.d_wb; p.bias = r->d_zero_alpha; p.alpha = dact ? r->d_zero_alpha : nullptr; p.dact = dact;
         p.resid = resid; p.out = out; p.zero = r->d_zero;
-        p.N = N; p.H = f.Ho; p.W = f.Wo; p.Cin = f.Cout; p.Cout = f.Cin; p.Ho = f.Ho; p.Wo = f.Wo; p.stride = 1; p.ksz = f.ksz;
-        p.pad = f.pad; p.M = N * f.Ho * f.Wo; p.splitk = 1; p.ksteps_per_split = f.ksz * f.ksz * (f.Cout / 64);
+        conv_geometry(p, N, f.Ho, f.Wo, f.Cout, f.Cin, f.ksz, 1, f.pad);
         ALINK_HIP(launch_conv(op.bkernel, dt, p, st));
         return ALINK_OK;
     };
@@ -1045,9 +917,8 @@ static int r50_input_grad(alink_resnet50_t* r, const float* dev_dfeat, int n_ima
     if ((rc = mark())) return rc;
     if (ms) {
         ALINK_HIP(hipStreamSynchronize(st));
-        int k = 0;
-        for (; k + 1 < (int)ev.size() && k < *n_stages; ++k) ALINK_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-        *n_stages = k;
+        if ((rc = timer.elapsed(ms, *n_stages))) return rc;
+        *n_stages = std::min(*n_stages, timer.intervals());
     }
     return ALINK_OK;
 }

@@ -14,6 +14,7 @@
 // The pair head (|l-r| -> 128 -> 32 -> 2) is an alink_head handle (head.hip); this file adds the
 // tower forward/backward and ties the two Adadelta states together.
 #include "alink_common.h"
+#include "net_host.h"
 #include "sgemm.h"
 #include "philox.h"
 
@@ -312,13 +313,12 @@ struct alink_smallres {
     float* ig_metrics = nullptr;       // {loss, accuracy} of alink_smallres_input_grad's head pass (nobody reads them)
     float* ws = nullptr;               // split-K slabs of sgemm
     size_t ws_floats = 0;
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
     ~alink_smallres() {
         for (auto& g : graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
         if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
         for (hipEvent_t e : ev_dz) if (e) (void)hipEventDestroy(e);
         if (ev_side) (void)hipEventDestroy(ev_side);
-        for (void* p : allocs) (void)hipFree(p);
         if (h_stage) (void)hipHostFree(h_stage);
         if (h_metrics) (void)hipHostFree(h_metrics);
         if (d_stage) (void)hipFree(d_stage);
@@ -331,10 +331,7 @@ namespace {
 
 template <typename V>
 int sr_alloc(alink_smallres* m, V** p, size_t count) {
-    ALINK_HIP(hipMalloc((void**)p, count * sizeof(V)));
-    m->allocs.push_back(*p);
-    ALINK_HIP(hipMemset(*p, 0, count * sizeof(V)));
-    return ALINK_OK;
+    return m->mem.zeros(count * sizeof(V), (void**)p);
 }
 
 const int CI[4] = {3, 32, 32, 64}, CO[4] = {32, 32, 64, 64}, PAD[4] = {1, 0, 1, 0};

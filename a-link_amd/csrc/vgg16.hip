@@ -13,6 +13,7 @@
 // bias slot, ReLU as a zero-slope PReLU epilogue).  New here: the 2x2 max-pool, whose last instance
 // writes the float32 features.
 #include "conv_device.h"
+#include "net_host.h"
 
 #include <algorithm>
 #include <cstring>
@@ -56,8 +57,6 @@ struct VOp {
     std::string name;
 };
 
-uint16_t cvt16(int dtype, float f) { return dtype == ALINK_DT_BF16 ? f32_to_bf16_rne(f) : f32_to_f16_rne(f); }
-
 }  // namespace
 }  // namespace alink
 
@@ -66,28 +65,18 @@ using namespace alink;
 struct alink_vgg16 {
     int device = -1;
     int H, W, dtype;
-    std::vector<std::pair<std::string, size_t>> expected;
-    std::map<std::string, std::vector<float>> raw;
+    TensorTable tensors;
     bool finalized = false;
+    DeviceAllocs mem;
     std::vector<VOp> ops;
     void* d_stem_w = nullptr;
     float *d_stem_bias = nullptr, *d_zero_alpha = nullptr;
     void* d_zero = nullptr;
     int Hf = 0, Wf = 0;
     size_t buf_elems_per_image = 0;
-    std::vector<void*> allocs;
-    ~alink_vgg16() { for (void* p : allocs) (void)hipFree(p); }
 };
 
 namespace {
-
-template <typename V>
-int upload(alink_vgg16* r, const std::vector<V>& h, void** d) {
-    ALINK_HIP(hipMalloc(d, h.size() * sizeof(V)));
-    r->allocs.push_back(*d);
-    ALINK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(V), hipMemcpyHostToDevice));
-    return ALINK_OK;
-}
 
 std::string lname(int b, int l) {
     char s[32];
@@ -108,8 +97,8 @@ alink_vgg16_t* alink_vgg16_create(int height, int width, int dtype) {
     int cin = 3;
     for (int b = 0; b < 5; ++b)
         for (int l = 0; l < kBlocks[b]; ++l) {
-            r->expected.emplace_back(lname(b, l) + "/kernel", (size_t)9 * cin * kWidth[b]);
-            r->expected.emplace_back(lname(b, l) + "/bias", (size_t)kWidth[b]);
+            r->tensors.expect(lname(b, l) + "/kernel", (size_t)9 * cin * kWidth[b]);
+            r->tensors.expect(lname(b, l) + "/bias", (size_t)kWidth[b]);
             cin = kWidth[b];
         }
     r->Hf = height >> 5; r->Wf = width >> 5;
@@ -121,49 +110,34 @@ void alink_vgg16_destroy(alink_vgg16_t* r) {
     DeviceGuard dg(r->device);
     delete r;
 }
-int alink_vgg16_num_tensors(const alink_vgg16_t* r) { return r ? (int)r->expected.size() : 0; }
+int alink_vgg16_num_tensors(const alink_vgg16_t* r) { return r ? r->tensors.count() : 0; }
 int alink_vgg16_tensor_info(const alink_vgg16_t* r, int i, const char** name, size_t* count) {
-    ALINK_REQUIRE(r && i >= 0 && i < (int)r->expected.size(), ALINK_EINVAL, "tensor index out of range");
-    if (name) *name = r->expected[i].first.c_str();
-    if (count) *count = r->expected[i].second;
-    return ALINK_OK;
+    ALINK_REQUIRE(r, ALINK_EINVAL, "tensor index out of range");
+    return r->tensors.info(i, name, count);
 }
 int alink_vgg16_feature_size(const alink_vgg16_t* r) { return r ? r->Hf * r->Wf * 512 : 0; }
 
 int alink_vgg16_load(alink_vgg16_t* r, const char* name, const float* host, size_t count) {
-    ALINK_REQUIRE(r && name && host, ALINK_EINVAL, "NULL argument");
-    ALINK_REQUIRE(!r->finalized, ALINK_ESTATE, "network already finalized");
-    for (const auto& e : r->expected)
-        if (e.first == name) {
-            ALINK_REQUIRE(e.second == count, ALINK_EINVAL, "tensor %s: expected %zu elements, got %zu", name, e.second, count);
-            r->raw[name].assign(host, host + count);
-            return ALINK_OK;
-        }
-    set_error("tensor %s is not part of the VGGFace VGG-16", name);
-    return ALINK_ENOTFOUND;
+    ALINK_REQUIRE(r, ALINK_EINVAL, "NULL argument");
+    return r->tensors.load(name, host, count, r->finalized, "the VGGFace VGG-16");
 }
 
 int alink_vgg16_finalize(alink_vgg16_t* r) {
     ALINK_REQUIRE(r && !r->finalized, ALINK_ESTATE, "bad state");
     DeviceGuard dg(r->device);
-    for (const auto& e : r->expected)
-        ALINK_REQUIRE(r->raw.count(e.first), ALINK_ESTATE, "tensor %s was never loaded", e.first.c_str());
-    int rc = init_kernels();
+    int rc = r->tensors.require_all_loaded();
     if (rc) return rc;
-    ALINK_HIP(hipMalloc(&r->d_zero, 4096));
-    r->allocs.push_back(r->d_zero);
-    ALINK_HIP(hipMemset(r->d_zero, 0, 4096));
-    ALINK_HIP(hipMalloc((void**)&r->d_zero_alpha, 512 * 4));
-    r->allocs.push_back(r->d_zero_alpha);
-    ALINK_HIP(hipMemset(r->d_zero_alpha, 0, 512 * 4));
+    if ((rc = init_kernels())) return rc;
+    if ((rc = r->mem.zeros(4096, &r->d_zero))) return rc;
+    if ((rc = r->mem.zeros(512 * 4, (void**)&r->d_zero_alpha))) return rc;
     {   // conv1_1: [64'][64] T, k = ky*16 + kx*3 + c (StemParams::wgt) from the Keras kernel (3,3,3,64)
-        const auto& w = r->raw.at("conv1_1/kernel");
-        std::vector<uint16_t> wq((size_t)64 * 64, cvt16(r->dtype, 0.f));
+        const auto& w = r->tensors.at("conv1_1/kernel");
+        std::vector<uint16_t> wq((size_t)64 * 64, cvt(r->dtype, 0.f));
         for (int co = 0; co < 64; ++co)
             for (int k = 0; k < 27; ++k)
-                wq[(size_t)perm64_row_of_channel(co) * 64 + (k / 9) * 16 + k % 9] = cvt16(r->dtype, w[(size_t)k * 64 + co]);
-        if ((rc = upload(r, wq, &r->d_stem_w))) return rc;
-        if ((rc = upload(r, r->raw.at("conv1_1/bias"), (void**)&r->d_stem_bias))) return rc;
+                wq[(size_t)perm64_row_of_channel(co) * 64 + (k / 9) * 16 + k % 9] = cvt(r->dtype, w[(size_t)k * 64 + co]);
+        if ((rc = r->mem.upload(wq, &r->d_stem_w))) return rc;
+        if ((rc = r->mem.upload(r->tensors.at("conv1_1/bias"), (void**)&r->d_stem_bias))) return rc;
     }
     int H = r->H, W = r->W, cin = 64, cur = 0;
     r->buf_elems_per_image = (size_t)H * W * 64;
@@ -171,23 +145,20 @@ int alink_vgg16_finalize(alink_vgg16_t* r) {
     for (int b = 0; b < 5; ++b) {
         for (int l = (b == 0 ? 1 : 0); l < kBlocks[b]; ++l) {
             const int cout = kWidth[b];
-            const auto& w = r->raw.at(lname(b, l) + "/kernel");       // (3, 3, cin, cout)
+            const auto& w = r->tensors.at(lname(b, l) + "/kernel");       // (3, 3, cin, cout)
             VOp op; op.kind = 1; op.name = lname(b, l);
             op.kernel = direct_variant_tiles(3, 1, 1, H, W, cin, cout);
-            const WeightLayout wl = weight_layout(op.kernel, 3, cin);
-            std::vector<uint16_t> wq(wl.size(cout));
-            for (int co = 0; co < cout; ++co)
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int ci = 0; ci < cin; ++ci) wq[wl.at(co, tap, ci)] = cvt16(r->dtype, w[((size_t)tap * cin + ci) * cout + co]);
+            const std::vector<uint16_t> wq =
+                pack_conv_weights(weight_layout(op.kernel, 3, cin), r->dtype, Round16::ViaFloat32, cout,
+                                  [&](int co, int tap, int ci) { return (double)w[((size_t)tap * cin + ci) * cout + co]; }).w;
             void* d_w = nullptr;
             float* d_b = nullptr;
-            if ((rc = upload(r, wq, &d_w))) return rc;
-            if ((rc = upload(r, r->raw.at(lname(b, l) + "/bias"), (void**)&d_b))) return rc;
+            if ((rc = r->mem.upload(wq, &d_w))) return rc;
+            if ((rc = r->mem.upload(r->tensors.at(lname(b, l) + "/bias"), (void**)&d_b))) return rc;
             ConvParams& p = op.cp;
             memset(&p, 0, sizeof(p));
             p.wgt = d_w; p.bias = d_b; p.alpha = r->d_zero_alpha; p.zero = r->d_zero;
-            p.H = H; p.W = W; p.Cin = cin; p.Cout = cout; p.Ho = H; p.Wo = W; p.stride = 1; p.ksz = 3; p.pad = 1;
-            p.splitk = 1; p.ksteps_per_split = 9 * (cin / 64);
+            conv_geometry(p, 0, H, W, cin, cout, 3, 1, 1);       // N, M: with_batch, per call
             op.in_buf = cur; op.out_buf = cur ^ 1; cur ^= 1;
             r->ops.push_back(op);
             r->buf_elems_per_image = std::max(r->buf_elems_per_image, (size_t)H * W * cout);
@@ -198,7 +169,7 @@ int alink_vgg16_finalize(alink_vgg16_t* r) {
         r->ops.push_back(mp);
         H /= 2; W /= 2;
     }
-    r->raw.clear();
+    r->tensors.clear();
     r->finalized = true;
     return ALINK_OK;
 }
@@ -232,7 +203,7 @@ int alink_vgg16_embed(alink_vgg16_t* r, const float* dev_in, int n, int preproce
             ALINK_HIP(launch_stem(r->dtype, sp, st));
         } else if (op.kind == 1) {
             ConvParams p = op.cp;
-            p.in = buf(op.in_buf); p.out = buf(op.out_buf); p.N = n; p.M = n * p.Ho * p.Wo;
+            p.in = buf(op.in_buf); p.out = buf(op.out_buf); with_batch(p, n);
             ALINK_HIP(launch_conv(op.kernel, r->dtype, p, st));
         } else {
             const bool last = i + 1 == nops;

@@ -85,7 +85,9 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
     // diagnostic (alink_debug_set_stamps; nullptr in every product call): 8 x u64 per workgroup — start, main loop
     // entered, main loop left, end (stores drained), cycles inside the input refills, number of refills, residual
     // loads returned, last store issued
-    unsigned long long* const stamps = (unsigned long long*)p.stamps;
+    // (the compile-time forward forms EPI 1 / 2 are never launched with stamps: there the diagnostic is compiled out, and
+    // with it the branch between the epilogue's residual loads and their first use that kept the waits uncounted)
+    unsigned long long* const stamps = (EPI == 1 || EPI == 2) ? nullptr : (unsigned long long*)p.stamps;
     unsigned long long refill_cycles = 0;
     if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 8 + 0] = __builtin_amdgcn_s_memtime();
     // split mode (small batches: too few workgroups to fill the chip): blockIdx.y owns ncc / splitk of the
@@ -151,11 +153,33 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
         }
     };
 
-    // The first input span and the first weight tile are requested NOW: the per-lane border bits (integer divisions),
-    // the accumulator clear and the bias / slope tables below all run under their flight instead of before it
-    // (stamps: the prologue of a 512-workgroup stage-3 launch took 9.0 k of the workgroup's 100 k cycles).
+    // The first input span and the first weight tile are requested NOW, and the bias / slope table loads right behind them
+    // (one batch, no wait in between), so that the per-lane border bits (integer divisions) and the accumulator clear run
+    // under their flight.  Two things keep it that way in the compiled kernel, not only in the source: the table loads
+    // are unrolled into registers ahead of a single wait (as a rolled copy loop each trip was load -> vmcnt(0) -> ds_write,
+    // up to six exposed round trips, the first of which — vmcnt counts in order — also waited for every DMA), and the
+    // finished border word and accumulators are pinned above the barrier (its asm statement orders memory accesses only:
+    // left alone the compiler sank ~400 instructions, the quarter-rate multiplies of the divisions among them, below it,
+    // where nothing was in flight any more and the "main loop entered" stamp booked them to the main loop).
+    // (stamps: the prologue of a 512-workgroup stage-3 launch took 9.0 k of the workgroup's 100 k cycles.)
     stage_x(cc_first);
     stage_w(0);
+    // bias (one row of BN per border class) and PReLU slope tables: every load before the first wait.  A slot past the
+    // run-time table end (one class instead of nine, the half-empty last trip, no slopes) loads entry 0 of the bias
+    // instead of branching — unconditional loads are what lets them all issue together — and is not written to LDS.
+    const int ncls = p.border_cls ? 9 : 1;
+    constexpr int TBL_TRIPS = (9 * BN + NT - 1) / NT;
+    static_assert(BN <= NT, "the slope table is one trip");
+    float tbias[TBL_TRIPS], talpha;
+#pragma unroll
+    for (int k = 0; k < TBL_TRIPS; ++k) {
+        const int i = tid + NT * k;
+        tbias[k] = p.bias[i < ncls * BN ? (i / BN) * p.Cout + n0 + (i % BN) : 0];
+    }
+    {
+        const float* ap = p.alpha ? p.alpha + n0 + (tid < BN ? tid : 0) : p.bias;
+        talpha = *ap;
+    }
 
     // ---- per-lane fragment offsets and border bits --------------------------------------------------------------
     const int dl = delta(lr);
@@ -189,12 +213,21 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
 #pragma unroll
         for (int u = 0; u < TPW; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int ncls = p.border_cls ? 9 : 1;
+    // pinned: volatile asm statements keep their order, so these values are complete before the barrier's statement
+    asm volatile("" : "+v"(border));
+#pragma unroll
+    for (int t = 0; t < TCW; ++t)
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) asm volatile("" : "+v"(acc[t][u]));
+
     float* const ebias = (float*)(smem + G::WOFF + 2 * WBYTES);
     float* const ealpha = ebias + 9 * BN;
-    for (int i = tid; i < ncls * BN; i += NT) ebias[i] = p.bias[(i / BN) * p.Cout + n0 + (i % BN)] * (SP ? p.bias_scale : 1.f);
-    if (p.alpha)
-        for (int i = tid; i < BN; i += NT) ealpha[i] = p.alpha[n0 + i];
+#pragma unroll
+    for (int k = 0; k < TBL_TRIPS; ++k) {
+        const int i = tid + NT * k;
+        if (i < ncls * BN) ebias[i] = tbias[k] * (SP ? p.bias_scale : 1.f);
+    }
+    if (p.alpha && tid < BN) ealpha[tid] = talpha;
     wait_then_barrier<0>();
     if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memtime();
 
@@ -354,77 +387,92 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
         }
         return;
     }
-    size_t off[TPW];
-    bool ok[TPW];
-    int cls[TPW];
+    // Two forms of the same code.  A workgroup whose 224 pixels all exist (gp0 + GPX <= totpix, workgroup-uniform: every
+    // group but a launch's ragged last one) runs it WITHOUT the per-tile `ok` predicate: as real branches those made the
+    // compiler merge, at every join, a path on which the residual loads were still pending, and emit s_waitcnt vmcnt(0)
+    // in each of the seven tile blocks — and since stores count in vmcnt too, tiles 2-7 each waited for the previous
+    // tile's two stores to be acknowledged: six serial store round trips per wave.  That, not the residual read, is what
+    // the residual epilogue waited on (the PReLU form has no pending loads and never had those waits).  In straight-line
+    // code the compiler can count: one wait for the residual loads, then fourteen stores with no wait between them.
+    auto epilogue16 = [&](auto fullc) {
+        constexpr bool FULL = decltype(fullc)::a != 0;
+        size_t off[TPW];
+        bool ok[TPW];
+        int cls[TPW];
 #pragma unroll
-    for (int u = 0; u < TPW; ++u) {
-        const long long gp = gp0 + 16 * (wpx * TPW + u) + dl;
-        ok[u] = gp < totpix;
-        off[u] = (size_t)(ok[u] ? gp : 0) * p.Cout + n0;
-        const unsigned b4 = (border >> (4 * u)) & 15u;
-        const int rc = (b4 & 1u) ? 0 : ((b4 & 2u) ? 2 : 1);
-        const int ccl = (b4 & 4u) ? 0 : ((b4 & 8u) ? 2 : 1);
-        cls[u] = p.border_cls ? rc * 3 + ccl : 0;
-    }
-    vec8 res[TPW][CPL / 8];
-    const T* extra = EPI == 1 ? (const T*)nullptr : (const T*)((EPI == 0 && p.dact) ? p.dact : p.resid);
-    if (EPI == 2 || (EPI == 0 && extra)) {
-#pragma unroll
-        for (int u = 0; u < TPW; ++u)
-#pragma unroll
-            for (int h = 0; h < CPL / 8; ++h) res[u][h] = *(const vec8*)(extra + off[u] + chan_h(h));
-    }
-    if (stamps) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memtime();
-    }
-#pragma unroll
-    for (int u = 0; u < TPW; ++u) {
-        float v[CPL];
-#pragma unroll
-        for (int t = 0; t < TCW; ++t) {
-            const f32x4 b4 = *(const f32x4*)(ebias + cls[u] * BN + chan_t(t));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[4 * t + j] = acc[t][u][j] + b4[j];
+        for (int u = 0; u < TPW; ++u) {
+            const long long gp = gp0 + 16 * (wpx * TPW + u) + dl;
+            ok[u] = FULL || gp < totpix;
+            off[u] = (size_t)(FULL || ok[u] ? gp : 0) * p.Cout + n0;
+            const unsigned b4 = (border >> (4 * u)) & 15u;
+            const int rc = (b4 & 1u) ? 0 : ((b4 & 2u) ? 2 : 1);
+            const int ccl = (b4 & 4u) ? 0 : ((b4 & 8u) ? 2 : 1);
+            cls[u] = p.border_cls ? rc * 3 + ccl : 0;
         }
-        if (EPI == 0 && p.dact) {
+        vec8 res[TPW][CPL / 8];
+        const T* extra = EPI == 1 ? (const T*)nullptr : (const T*)((EPI == 0 && p.dact) ? p.dact : p.resid);
+        if (EPI == 2 || (EPI == 0 && extra)) {
+#pragma unroll
+            for (int u = 0; u < TPW; ++u)
+#pragma unroll
+                for (int h = 0; h < CPL / 8; ++h) res[u][h] = *(const vec8*)(extra + off[u] + chan_h(h));
+            // all fourteen loads are issued before anything consumes one: left to itself the scheduler started on tile 0
+            // after its two loads, a full round trip with the other twelve not yet requested
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (stamps) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (tid == 0) stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memtime();
+        }
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            float v[CPL];
 #pragma unroll
             for (int t = 0; t < TCW; ++t) {
-                const f32x4 a4 = *(const f32x4*)(ealpha + chan_t(t));
+                const f32x4 b4 = *(const f32x4*)(ebias + cls[u] * BN + chan_t(t));
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[4 * t + j] *= (float)res[u][(4 * t + j) / 8][(4 * t + j) % 8] > 0.f ? 1.f : a4[j];
+                for (int j = 0; j < 4; ++j) v[4 * t + j] = acc[t][u][j] + b4[j];
             }
-        } else {
-            if (EPI == 1 || (EPI == 0 && p.alpha)) {
+            if (EPI == 0 && p.dact) {
 #pragma unroll
                 for (int t = 0; t < TCW; ++t) {
                     const f32x4 a4 = *(const f32x4*)(ealpha + chan_t(t));
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) v[4 * t + j] = v[4 * t + j] > 0.f ? v[4 * t + j] : v[4 * t + j] * a4[j];
+                    for (int j = 0; j < 4; ++j) v[4 * t + j] *= (float)res[u][(4 * t + j) / 8][(4 * t + j) % 8] > 0.f ? 1.f : a4[j];
+                }
+            } else {
+                if (EPI == 1 || (EPI == 0 && p.alpha)) {
+#pragma unroll
+                    for (int t = 0; t < TCW; ++t) {
+                        const f32x4 a4 = *(const f32x4*)(ealpha + chan_t(t));
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[4 * t + j] = v[4 * t + j] > 0.f ? v[4 * t + j] : v[4 * t + j] * a4[j];
+                    }
+                }
+                if (EPI == 2 || (EPI == 0 && p.resid)) {
+#pragma unroll
+                    for (int h = 0; h < CPL / 8; ++h)
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) v[8 * h + i] += (float)res[u][h][i];
                 }
             }
-            if (EPI == 2 || (EPI == 0 && p.resid)) {
+            if (EPI == 0 && p.post_relu) {
 #pragma unroll
-                for (int h = 0; h < CPL / 8; ++h)
+                for (int i = 0; i < CPL; ++i) v[i] = relu_keep_nan(v[i]);
+            }
+            if (FULL || ok[u]) {
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) v[8 * h + i] += (float)res[u][h][i];
+                for (int h = 0; h < CPL / 8; ++h) {
+                    vec8 o8;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) o8[i] = (T)v[8 * h + i];
+                    *(vec8*)((T*)p.out + off[u] + chan_h(h)) = o8;
+                }
             }
         }
-        if (EPI == 0 && p.post_relu) {
-#pragma unroll
-            for (int i = 0; i < CPL; ++i) v[i] = relu_keep_nan(v[i]);
-        }
-        if (ok[u]) {
-#pragma unroll
-            for (int h = 0; h < CPL / 8; ++h) {
-                vec8 o8;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) o8[i] = (T)v[8 * h + i];
-                *(vec8*)((T*)p.out + off[u] + chan_h(h)) = o8;
-            }
-        }
-    }
+    };
+    if (gp0 + GPX <= totpix) epilogue16(IC<1>{});
+    else                     epilogue16(IC<0>{});
     if (stamps && tid == 0) {
         stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -25,6 +25,18 @@ class IRCfg(C.Structure):
 
 
 _vp, _i, _i64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
+
+
+class Gemm32Desc(C.Structure):
+    """alink_gemm32_desc (include/alink_hip.h)"""
+    _fields_ = ([(n, _vp) for n in ("A", "B", "C", "A2")] + [("a_split", _i)]
+                + [(n, _i) for n in ("M", "N", "K", "lda", "ldb", "ldc", "amode", "bmode")]
+                + [(n, _i) for n in ("H", "W", "Ci", "Ho", "Wo", "pad", "prescale", "ks", "cstride")]
+                + [("pre_sub", _f), ("pre_mul", _f)]
+                + [(n, _vp) for n in ("bias", "act", "alpha", "resid")]
+                + [(n, _i) for n in ("relu", "accumulate", "splitk", "kper", "force_bk")])
+
+
 _u64 = C.c_uint64
 _fp = C.POINTER(C.c_float)
 
@@ -60,6 +72,7 @@ PROTOTYPES = {
     "alink_conv_nhwc_ex": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 10 + [_i, _vp, _i, _vp, _vp, _i, _i, _i]
                            + [C.POINTER(_i), C.POINTER(_i), _vp]),
     "alink_conv_nhwc_x2_ex": (_i, [_vp] * 6 + [_i] * 14 + [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "alink_gemm32_ex": (_i, [C.POINTER(Gemm32Desc), _i, _vp, _sz, C.POINTER(_i), _vp]),
     "alink_resnet50_create": (_vp, [_i, _i, _i, _f]),
     "alink_resnet50_destroy": (None, [_vp]),
     "alink_resnet50_num_tensors": (_i, [_vp]),

@@ -40,6 +40,9 @@ size_t     gemm32_workspace_floats(const GemmP& p);
 // the stage depth (16 or 64) the launcher picks for a PLANNED p (splitk, kper set) with force_bk == 0
 int        gemm32_stage_depth(const GemmP& p);
 hipError_t launch_gemm32(const GemmP& p, float* workspace, hipStream_t st);
+// what launch_gemm32 runs for a PLANNED p, from the launcher's own predicates:
+// {tile columns (32 | 64), stage depth (16 | 64), 16-byte loaders (0 | 1), splitk, kper}
+void       gemm32_report(const GemmP& p, int out[5]);
 // out[i] = sum_z part[z][i], i < MN, z < S — the split-K slab sum on its own (fixed order: 8 interleaved groups, then the groups)
 hipError_t launch_slab_sum(const float* part, float* out, long long MN, int S, hipStream_t st);
 

@@ -511,6 +511,11 @@ inline bool vec_ok(const GemmP& p) {
     return a && b && ((((uintptr_t)p.A) | ((uintptr_t)p.B) | ((uintptr_t)(p.A2 ? p.A2 : p.A))) & 15) == 0;
 }
 
+// the stage depth of a planned p: the caller's (force_bk) or the grid's (deep()), and deep only where the slabs are whole deep stages
+inline int stage_of(const GemmP& p) {
+    return (p.force_bk ? p.force_bk == BK_DEEP : deep(p)) && (p.kper % BK_DEEP) == 0 ? BK_DEEP : BK_SMALL;
+}
+
 template <int WNv, int BKv>
 constexpr size_t lds_bytes() { return (size_t)BKv * ((32 * (4 / WNv) + 32) + 96) * sizeof(float); }
 
@@ -544,7 +549,7 @@ hipError_t launch_v(const GemmP& p, dim3 grid, hipStream_t st) {
 
 template <int AM, int BMo>
 hipError_t launch_t(const GemmP& p, hipStream_t st) {
-    const bool dp = (p.force_bk ? p.force_bk == BK_DEEP : deep(p)) && (p.kper % BK_DEEP) == 0;
+    const bool dp = stage_of(p) == BK_DEEP;
     if (narrow(p)) {
         dim3 grid((p.N + 31) / 32, (p.M + 127) / 128, p.splitk);
         const hipError_t e = dp ? launch_v<AM, BMo, 1, BK_DEEP>(p, grid, st) : launch_v<AM, BMo, 1, BK_SMALL>(p, grid, st);
@@ -560,6 +565,14 @@ hipError_t launch_t(const GemmP& p, hipStream_t st) {
 }  // namespace
 
 int gemm32_stage_depth(const GemmP& p) { return deep(p) && (p.kper % BK_DEEP) == 0 ? BK_DEEP : BK_SMALL; }
+
+void gemm32_report(const GemmP& p, int out[5]) {
+    out[0] = narrow(p) ? 32 : 64;
+    out[1] = stage_of(p);
+    out[2] = vec_ok(p) ? 1 : 0;
+    out[3] = p.splitk;
+    out[4] = p.kper;
+}
 
 size_t gemm32_workspace_floats(const GemmP& p) { return p.splitk > 1 ? (size_t)p.splitk * p.M * p.ldc : 0; }
 
@@ -608,3 +621,33 @@ hipError_t launch_slab_sum(const float* part, float* out, long long MN, int S, h
 }
 
 }  // namespace alink
+
+// ---- diagnostic single-GEMM entry (unit tests) --------------------------------------------------
+extern "C" int alink_gemm32_ex(const alink_gemm32_desc* d, int max_split, float* dev_workspace, size_t workspace_floats,
+                               int* report, void* stream) {
+    using namespace alink;
+    if (report) for (int i = 0; i < 5; ++i) report[i] = -1;
+    ALINK_REQUIRE(d && d->A && d->B && d->C, ALINK_EINVAL, "NULL argument");
+    ALINK_REQUIRE(max_split >= 0, ALINK_EINVAL, "max_split must be >= 0");
+    DeviceGuard dg(device_of_pointer(d->C));
+    GemmP g{};
+    g.A = d->A; g.B = d->B; g.C = d->C; g.A2 = d->A2; g.a_split = d->a_split;
+    g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
+    g.amode = d->amode; g.bmode = d->bmode;
+    g.H = d->H; g.W = d->W; g.Ci = d->Ci; g.Ho = d->Ho; g.Wo = d->Wo; g.pad = d->pad; g.prescale = d->prescale;
+    g.ks = d->ks; g.cstride = d->cstride; g.pre_sub = d->pre_sub; g.pre_mul = d->pre_mul;
+    g.bias = d->bias; g.act = d->act; g.alpha = d->alpha; g.resid = d->resid;
+    g.relu = d->relu; g.accumulate = d->accumulate;
+    g.splitk = d->splitk; g.kper = d->kper; g.force_bk = d->force_bk;
+    ALINK_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, ALINK_EINVAL, "M, N, K must be positive");
+    if (max_split >= 1) gemm32_plan_split(g, max_split);
+    ALINK_REQUIRE(g.splitk >= 1, ALINK_EINVAL, "splitk must be >= 1");
+    // (a split without any workspace is the launcher's to refuse)
+    ALINK_REQUIRE(!dev_workspace || gemm32_workspace_floats(g) <= workspace_floats, ALINK_ENOMEM,
+                  "sgemm workspace too small (%zu floats needed, %zu given)", gemm32_workspace_floats(g), workspace_floats);
+    hipStream_t st = (hipStream_t)stream;
+    ALINK_HIP(launch_gemm32(g, dev_workspace, st));      // (its refusals come before its first launch)
+    if (report) gemm32_report(g, report);
+    ALINK_HIP(hipStreamSynchronize(st));
+    return ALINK_OK;
+}

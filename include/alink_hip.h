@@ -215,6 +215,44 @@ int alink_conv_nhwc_x2_ex(const float* dev_in, const float* dev_w, const float* 
                           int stride, int pad, int border_cls, int fine, int e_in, int e_w, int e_out, int e_res,
                           int nprod, int splitk, int post_relu, int* kernel_out, int* form_out, void* stream);
 
+/* alink_gemm32_ex: ONE launch of the exact-f32 GEMM (csrc/sgemm.hip: SmallRes, the float32 backbone mode, the margin loss) with
+ * every caller-settable field of its launch descriptor in the caller's hands, and a report of what ran.  C[M][N] = A[M][K] . B[K][N],
+ * all operands float32 on the device; the fields are those of alink::GemmP (csrc/sgemm.h), which documents them:
+ *   amode  0 = A row-major [M][lda], 1 = A given as [K][lda] (columns = m), 2 = im2col gather of an NHWC tensor (m = (n, oy, ox),
+ *          k = (ky, kx, ci)), 3 = its transpose with the reduction over pixels and one extra row of ones (M = 9 Ci + 1)
+ *   bmode  0 = B row-major [K][ldb], 1 = B given as [N][ldb], 2 = 3x3 weights (ky, kx, ci, co) flipped and transposed (input gradient)
+ *   max_split  >= 1: the split along K is planned as production plans it (gemm32_plan_split with this limit; d->splitk and
+ *              d->kper are ignored); 0: the caller's d->splitk / d->kper are used as they stand — the fixed plans of
+ *              alink_smallres_score_pairs and of the float32 backbone's FC
+ *   dev_workspace, workspace_floats: the split's partial slabs, splitk x M x ldc floats; may be NULL / 0 for an unsplit launch
+ *   report     NULL, or int[5] = { tile columns (32: the 128 x 32 tile, 64: the 64 x 64 tile), stage depth (16 | 64),
+ *              loaders (1: 16-byte, 0: 4-byte), splitk, kper } as the launcher itself decides them; all -1 when the call is refused
+ * A request the launcher rejects (a split with ldc != N or without workspace, bmode 2 with Ci % 4 != 0 or amode != 2, a mode pair
+ * without a kernel, kper no multiple of 16, force_bk other than 0 / 16 / 64) or a workspace that is too small returns an error
+ * code with alink_last_error set and launches nothing.  Synchronous (test use only). */
+enum { ALINK_GEMM_A_ROW = 0, ALINK_GEMM_A_COL = 1, ALINK_GEMM_A_CONV = 2, ALINK_GEMM_A_CONVT = 3 };
+enum { ALINK_GEMM_B_ROW = 0, ALINK_GEMM_B_COLT = 1, ALINK_GEMM_B_FLIP = 2 };
+typedef struct alink_gemm32_desc {
+    const float* A;
+    const float* B;
+    float* C;
+    const float* A2;
+    int a_split;
+    int M, N, K, lda, ldb, ldc;
+    int amode, bmode;
+    int H, W, Ci, Ho, Wo, pad, prescale, ks, cstride;
+    float pre_sub, pre_mul;
+    const float* bias;
+    const float* act;
+    const float* alpha;
+    const float* resid;
+    int relu, accumulate;
+    int splitk, kper;
+    int force_bk;
+} alink_gemm32_desc;
+int alink_gemm32_ex(const alink_gemm32_desc* d, int max_split, float* dev_workspace, size_t workspace_floats, int* report,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * VGGFace2 ResNet-50 feature extractor: siamese.RESNET50 (code/siamese.py:203-216) =
  * keras_vggface VGGFace(model='resnet50', include_top=False) cut at 'avg_pool', flattened (2048-d),

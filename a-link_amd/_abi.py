@@ -171,6 +171,7 @@ PROTOTYPES = {
     "alink_arcface_margin_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "alink_contrastive_loss": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "alink_score": (_i, [_i, _vp, _vp, _i, _i64, _i, _vp, _vp]),
+    "alink_committee_disagreement": (_i, [C.POINTER(_vp), _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "alink_topk_scratch_bytes": (_sz, [_i64, _i]),
     "alink_topk": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "alink_identify_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -45,6 +45,37 @@ class Bagging:
             raise TypeError("predict_indexed needs DenseHead members")
         return _head.committee_predict_device(hs, emb_left, emb_right, li, ri)
 
+    def disagreement(self, predict_on, kind="vote_entropy"):
+        """Extension: how far the members DISAGREE on every pair of predict_on = [left, right] — `kind` is vote_entropy,
+        consensus_entropy or max_disagreement (disagreement.py; modAL.disagreement's measures), which predict's mean cannot
+        give.  DenseHead members: the members' probabilities and the measure stay on the GPU (one launch for the measure);
+        any other duck-typed member: the host formulas on the members' predict outputs."""
+        from . import disagreement as _dis
+        if kind not in _dis.KINDS:
+            raise ValueError("unknown disagreement kind %r: choose among %s" % (kind, list(_dis.KINDS)))
+        hs = self._device_heads()
+        if hs is not None:
+            probs = _head.committee_member_probs_device(hs, predict_on[0], predict_on[1])
+            out = _dis.score_members_device(probs, want=(kind,))[kind]
+            return out if isinstance(predict_on[0], hs[0].torch.Tensor) else out.cpu().numpy()
+        proba = np.stack([np.asarray(model.predict(predict_on)) for model in self.models], axis=1)       # (P, M, C)
+        if proba.ndim != 3 or proba.shape[2] < 2:
+            raise TypeError("committee disagreement needs class probabilities: a one-column member has no vote to count")
+        if kind == "vote_entropy":
+            return _dis.votes_entropy(np.argmax(proba, axis=2), range(proba.shape[2]))
+        return _dis.proba_consensus_entropy(proba) if kind == "consensus_entropy" else _dis.proba_max_disagreement(proba)
+
+    def disagreement_indexed(self, emb_left, emb_right, li, ri, kind="vote_entropy"):
+        """Extension: disagreement over pairs (li[p], ri[p]) gathered from embedding matrices on device, as predict_indexed."""
+        from . import disagreement as _dis
+        if kind not in _dis.KINDS:
+            raise ValueError("unknown disagreement kind %r: choose among %s" % (kind, list(_dis.KINDS)))
+        hs = self._device_heads()
+        if hs is None:
+            raise TypeError("disagreement_indexed needs DenseHead members")
+        probs = _head.committee_member_probs_device(hs, emb_left, emb_right, li, ri)
+        return _dis.score_members_device(probs, want=(kind,))[kind]
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

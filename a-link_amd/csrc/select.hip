@@ -245,6 +245,148 @@ __global__ __launch_bounds__(256) void identify_rows_kernel(const float* __restr
     }
 }
 
+// ---- committee disagreement (modAL.disagreement: vote entropy, consensus entropy, maximum KL; code/learners.py:12,287) ---------
+// thread = a pair (grid-strided over the pairs): its C contiguous floats of every member's slab, so neighbouring lanes read
+// neighbouring rows; VEC floats per load where C and the slabs' alignment allow.  Everything a pair needs lives in registers:
+// the members' running sum s[CMAX] (CMAX = the power of two at or above C, every class loop unrolled over it under the
+// wave-uniform guard c < C) and the vote counts, one byte per class (M <= 64 fits) in CMAX / 4 words.  The KL term needs the
+// finished sum, so the members' rows are read a second time: the same lines by the same lane, one M-row sweep later.
+struct DisagreeArgs {
+    const float* probs[ALINK_DISAGREE_MAX_MEMBERS];
+    int M, C;
+    long long P;
+    float *vote_entropy, *consensus_entropy, *max_disagreement, *consensus;
+    int32_t* votes;
+};
+
+template <int CMAX, int VEC>
+__device__ __forceinline__ void disagree_load_row(const float* __restrict__ row, int C, float (&x)[CMAX]) {
+#pragma unroll
+    for (int c = 0; c < CMAX; c += VEC) {
+        if (c < C) {                                 // C is a multiple of VEC: c < C covers c .. c + VEC - 1
+            if constexpr (VEC == 4) {
+                const float4 v = *(const float4*)(row + c);
+                x[c] = v.x; x[c + 1] = v.y; x[c + 2] = v.z; x[c + 3] = v.w;
+            } else if constexpr (VEC == 2) {
+                const float2 v = *(const float2*)(row + c);
+                x[c] = v.x; x[c + 1] = v.y;
+            } else {
+                x[c] = row[c];
+            }
+        }
+    }
+}
+
+template <int CMAX, int VEC>
+__global__ __launch_bounds__(256) void disagreement_kernel(const DisagreeArgs a) {
+#pragma clang fp contract(off)      // the two bit-equalities (head.hip's committee epilogue, score_kernel's entropy) are sums of rounded products
+    constexpr int NW = CMAX >= 4 ? CMAX / 4 : 1;
+    const int M = a.M, C = a.C;
+    const float Mf = (float)M;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.P; i += stride) {
+        float s[CMAX], x[CMAX];
+        unsigned int cnt[NW];
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) s[c] = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) cnt[w] = 0u;
+        for (int m = 0; m < M; ++m) {
+            disagree_load_row<CMAX, VEC>(a.probs[m] + i * C, C, x);
+            float best = -INFINITY;                 // `>`: the first maximum, and a NaN never wins (alink_identify_rows)
+            int vote = 0;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c) {
+                if (c < C) {
+                    if (x[c] > best) { best = x[c]; vote = c; }
+                    s[c] = m == 0 ? x[c] : s[c] + x[c];     // (p_0 + p_1) + ... in member order
+                }
+            }
+#pragma unroll
+            for (int w = 0; w < NW; ++w) cnt[w] += (vote >> 2) == w ? 1u << ((vote & 3) * 8) : 0u;
+            if (a.votes) a.votes[i * M + m] = vote;
+        }
+        if (a.vote_entropy) {
+            // a function of the MULTISET of counts: sum over v = 1 .. M, ascending, of (classes holding v votes) x t_v
+            float e = 0.f;
+            for (int v = 1; v <= M; ++v) {
+                int k = 0;
+#pragma unroll
+                for (int w = 0; w < NW; ++w)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) k += ((cnt[w] >> (8 * b)) & 255u) == (unsigned)v ? 1 : 0;
+                if (k) {
+                    const float f = (float)v / Mf;
+                    const float t = -f * logf(f);
+                    e += (float)k * t;
+                }
+            }
+            a.vote_entropy[i] = e;
+        }
+        if (a.consensus || a.consensus_entropy) {
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) x[c] = s[c] / Mf;        // one IEEE division: head.hip's final_div
+            if (a.consensus) {
+                float* o = a.consensus + i * C;
+#pragma unroll
+                for (int c = 0; c < CMAX; c += VEC) {
+                    if (c < C) {
+                        if constexpr (VEC == 4) *(float4*)(o + c) = make_float4(x[c], x[c + 1], x[c + 2], x[c + 3]);
+                        else if constexpr (VEC == 2) *(float2*)(o + c) = make_float2(x[c], x[c + 1]);
+                        else o[c] = x[c];
+                    }
+                }
+            }
+            if (a.consensus_entropy) {              // score_kernel's entropy branch, operation for operation
+                float t = 0.f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c)
+                    if (c < C) t += x[c];
+                float e = 0.f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c) {
+                    if (c < C) {
+                        const float q = x[c] / t;
+                        e += (q > 0.f) ? -q * logf(q) : 0.f;
+                    }
+                }
+                a.consensus_entropy[i] = e;
+            }
+        }
+        if (a.max_disagreement) {
+            float worst = 0.f;
+            for (int m = 0; m < M; ++m) {
+                disagree_load_row<CMAX, VEC>(a.probs[m] + i * C, C, x);
+                float r = 0.f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c)
+                    if (c < C) r += x[c];
+                float kl = 0.f;
+#pragma unroll
+                for (int c = 0; c < CMAX; ++c) {
+                    if (c < C) {
+                        const float ph = x[c] / r;
+                        // against the members' SUM: s >= every addend, so the ratio stays at or below M (1 + rounding)
+                        kl += (ph > 0.f) ? ph * logf(ph * Mf / s[c]) : 0.f;
+                    }
+                }
+                worst = m == 0 ? kl : fmaxf(worst, kl);
+            }
+            a.max_disagreement[i] = worst;
+        }
+    }
+}
+
+template <int CMAX>
+void launch_disagreement(int vec, unsigned blocks, hipStream_t st, const DisagreeArgs& a) {
+    if constexpr (CMAX >= 4) {
+        if (vec == 4) { hipLaunchKernelGGL((disagreement_kernel<CMAX, 4>), dim3(blocks), dim3(256), 0, st, a); return; }
+    }
+    if (vec >= 2) hipLaunchKernelGGL((disagreement_kernel<CMAX, 2>), dim3(blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((disagreement_kernel<CMAX, 1>), dim3(blocks), dim3(256), 0, st, a);
+}
+
 unsigned int next_pow2(unsigned int x) {
     unsigned int p = 1;
     while (p < x) p <<= 1;
@@ -270,6 +412,39 @@ int alink_score(int kind, const float* dev_probs, const float* dev_b, int col, i
     ALINK_REQUIRE(P > 0, ALINK_EINVAL, "negative P");
     hipLaunchKernelGGL(score_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, kind,
                        dev_probs, dev_b, col, (long long)P, C, dev_scores);
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+int alink_committee_disagreement(const float* const* dev_member_probs, int n_members, int64_t P, int C, float* dev_vote_entropy,
+                                 float* dev_consensus_entropy, float* dev_max_disagreement, float* dev_consensus,
+                                 int32_t* dev_votes, void* stream) {
+    ALINK_REQUIRE(n_members >= 1 && n_members <= ALINK_DISAGREE_MAX_MEMBERS, ALINK_EINVAL, "n_members=%d outside 1..%d", n_members,
+                  ALINK_DISAGREE_MAX_MEMBERS);
+    ALINK_REQUIRE(C >= 2 && C <= ALINK_DISAGREE_MAX_CLASSES, ALINK_EINVAL, "C=%d outside 2..%d", C, ALINK_DISAGREE_MAX_CLASSES);
+    ALINK_REQUIRE(P >= 0, ALINK_EINVAL, "negative P");
+    if (P == 0 || (!dev_vote_entropy && !dev_consensus_entropy && !dev_max_disagreement && !dev_consensus && !dev_votes)) return ALINK_OK;
+    ALINK_REQUIRE(dev_member_probs, ALINK_EINVAL, "NULL member array");
+    DisagreeArgs a;
+    uintptr_t bits = (uintptr_t)dev_consensus;       // every address a vector access starts from
+    for (int m = 0; m < ALINK_DISAGREE_MAX_MEMBERS; ++m) {
+        a.probs[m] = m < n_members ? dev_member_probs[m] : nullptr;
+        ALINK_REQUIRE(m >= n_members || a.probs[m], ALINK_EINVAL, "NULL probabilities of member %d", m);
+        bits |= (uintptr_t)a.probs[m];
+    }
+    DeviceGuard dg(device_of_pointer(a.probs[0]));
+    a.M = n_members; a.C = C; a.P = (long long)P;
+    a.vote_entropy = dev_vote_entropy; a.consensus_entropy = dev_consensus_entropy; a.max_disagreement = dev_max_disagreement;
+    a.consensus = dev_consensus; a.votes = dev_votes;
+    const int vec = (C % 4 == 0 && bits % 16 == 0) ? 4 : (C % 2 == 0 && bits % 8 == 0) ? 2 : 1;
+    const long long nb = (P + 255) / 256;
+    const unsigned blocks = nb < 65536 ? (unsigned)nb : 65536u;     // the kernel strides over the pairs
+    hipStream_t st = (hipStream_t)stream;
+    if (C <= 2) launch_disagreement<2>(vec, blocks, st, a);
+    else if (C <= 4) launch_disagreement<4>(vec, blocks, st, a);
+    else if (C <= 8) launch_disagreement<8>(vec, blocks, st, a);
+    else if (C <= 16) launch_disagreement<16>(vec, blocks, st, a);
+    else launch_disagreement<32>(vec, blocks, st, a);
     ALINK_HIP(hipGetLastError());
     return ALINK_OK;
 }

@@ -207,9 +207,12 @@ def committee_pool_topk(backbones, heads, pool_shard, gallery, k, shard_offset, 
     (n, H, W, 3) and the replicated gallery are embedded by every committee member's backbone, each member's head
     scores the n * g (pool, gallery) pairs on its own embeddings, Bagging mean (reference code/committee.py:13-20),
     uncertainty measure `kind` (code/uncertainty.py), local exact top-k, ONE candidate exchange (merge_topk).
+    kind "vote_entropy" / "consensus_entropy" / "max_disagreement": the query-by-committee measure of that name
+    (disagreement.py) on the members' own probabilities instead of an uncertainty measure of their mean.
     Returns (scores, global pair index) of the job-wide top-k, identical on every rank; pair index =
     (shard_offset + i) * g + j for pool image i of this shard and gallery image j."""
     import torch
+    from . import disagreement as _dis
     from . import head as _head
     from . import uncertainty as _unc
     dist = _dist()
@@ -219,8 +222,12 @@ def committee_pool_topk(backbones, heads, pool_shard, gallery, k, shard_offset, 
     dev = heads[0].device
     li = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(g)
     ri = torch.arange(g, dtype=torch.int32, device=dev).repeat(n)
-    probs = _head.committee_predict_device(heads, Ep, Eg, li, ri)
-    scores = _unc.score_device(probs, kind)
+    if kind in _dis.KINDS:
+        # how far the members disagree (modAL.disagreement): each member's own probabilities, no mean taken first
+        scores = _dis.score_members_device(_head.committee_member_probs_device(heads, Ep, Eg, li, ri), want=(kind,))[kind]
+    else:
+        probs = _head.committee_predict_device(heads, Ep, Eg, li, ri)
+        scores = _unc.score_device(probs, kind)
     kk = min(k, scores.numel())
     idx, vals = _unc.topk_device(scores, kk, largest=True)
     gidx = idx.to(torch.int64) + int(shard_offset) * g

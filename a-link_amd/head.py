@@ -559,3 +559,28 @@ def committee_predict_device(heads, L, R, li=None, ri=None):
     _abi.check(h0.lib.alink_committee_forward(arr, len(heads), _abi.ptr(L), _abi.ptr(R), _abi.ptr(li), _abi.ptr(ri),
                                               P, _abi.ptr(out), None, _abi.current_stream(h0.device)), "alink_committee_forward")
     return out
+
+
+def committee_member_probs_device(heads, L, R, li=None, ri=None):
+    """Every member's own probabilities, WITHOUT the mean: (M, P, out_dim) CUDA float32, slab m written in place by
+    heads[m].predict_device (alink_head_forward) — what the query-by-committee measures need, which the mean of
+    committee_predict_device has already lost (disagreement.score_members_device).  L / R: shared matrices, or a list
+    with one matrix per member, as committee_predict_device takes them."""
+    h0 = heads[0]
+    torch = h0.torch
+    if any(h.out_dim == 1 for h in heads):
+        raise TypeError("committee disagreement needs class probabilities: a one-column (out_dim == 1) member has no vote to count")
+    if any(h.out_dim != h0.out_dim for h in heads):
+        raise ValueError("committee members differ in out_dim")
+    per_member = isinstance(L, (list, tuple))
+    if per_member and (len(L) != len(heads) or len(R) != len(heads)):
+        raise ValueError("%d members but %d / %d feature matrices" % (len(heads), len(L), len(R)))
+    if li is not None:
+        li, ri = h0._dev(li, torch.int32), h0._dev(ri, torch.int32)
+        P = li.numel()
+    else:
+        P = len(L[0] if per_member else L)
+    out = torch.empty((len(heads), P, h0.out_dim), dtype=torch.float32, device=h0.device)
+    for m, h in enumerate(heads):
+        h.predict_device(L[m] if per_member else L, R[m] if per_member else R, li, ri, out=out[m])
+    return out

@@ -552,6 +552,34 @@ int alink_smallres_mask_sizes(const alink_smallres_t* m, int* per_image_1, int* 
 #define ALINK_SCORE_DISPARITY   3   /* -|a[:,col] - b[:,col]| (needs dev_b)         */
 int alink_score(int kind, const float* dev_probs, const float* dev_b, int col, int64_t P, int C,
                 float* dev_scores, void* stream);
+/* Query-by-committee disagreement (modAL.disagreement, which the reference imports at code/learners.py:12 and names as
+ * Committee's query strategies at code/learners.py:245,287) of n_members committee members over P pairs.
+ * dev_member_probs: HOST array of n_members DEVICE pointers, member m's (P, C) float32 class probabilities (as
+ * alink_committee_forward_multi takes its matrices).  Every output may be NULL; all requested outputs come from ONE pass
+ * (one launch; the maximum-KL term reads each member's row a second time once the members' sum is complete).  Over pair
+ * i, member m, class c, with M = n_members:
+ *   votes[i][m]          = the first c that maximises p_m[i][c] (np.argmax); `>` comparisons, a NaN never wins.
+ *   consensus[i][c]      = ((p_0 + p_1) + ... + p_{M-1}) / (float)M, in member order with one IEEE division: bit-equal to
+ *                          what alink_committee_forward / _multi write for the same members.
+ *   consensus_entropy[i] = -sum_c q ln q over the renormalised consensus, q > 0 terms only: bit-equal to
+ *                          alink_score(ALINK_SCORE_ENTROPY) of the consensus.
+ *   max_disagreement[i]  = max_m sum_c ph ln(ph M / s_c): ph = member m's row renormalised (ph > 0 terms only), s_c the
+ *                          members' SUM, so the ratio is at most M (1 + rounding) and finite even where the divided mean
+ *                          of denormal probabilities underflows to 0 (scipy.stats.entropy(pk, qk) per member, then the
+ *                          maximum; the consensus is taken as it is: rows are probabilities, summing to 1 within rounding).
+ *   vote_entropy[i]      = -sum_c (n_c / M) ln(n_c / M) over the vote counts n_c, computed as sum over v = 1 .. M ascending of
+ *                          k_v t_v (k_v = classes holding v votes, t_v = -(v / M) logf(v / M)): a function of the MULTISET of
+ *                          counts, so equal disagreement is an exact tie and alink_topk's lower-index rule decides it.
+ * 1 <= n_members <= 64, 2 <= C <= 32 (else ALINK_EINVAL); P == 0 writes nothing; any P runs (the kernel strides). */
+#define ALINK_DISAGREE_MAX_MEMBERS 64
+#define ALINK_DISAGREE_MAX_CLASSES 32
+int alink_committee_disagreement(const float* const* dev_member_probs, int n_members, int64_t P, int C,
+                                 float* dev_vote_entropy,      /* (P)                                     */
+                                 float* dev_consensus_entropy, /* (P)                                     */
+                                 float* dev_max_disagreement,  /* (P)                                     */
+                                 float* dev_consensus,         /* (P, C)                                  */
+                                 int32_t* dev_votes,           /* (P, n_members): argmax class per member */
+                                 void* stream);
 /* indices of the k smallest (largest=0) or largest scores, ties broken by lower index, returned
  * sorted by (score, index).  dev_scratch >= alink_topk_scratch_bytes(P, k). */
 size_t alink_topk_scratch_bytes(int64_t P, int k);

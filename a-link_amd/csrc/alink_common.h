@@ -93,6 +93,8 @@ struct ConvParams {
     int fine;             // linear-tile kernel: 1 = 64-channel workgroups instead of 128 (small batches: twice the
                           // workgroups, same weights, bit-identical sums)
     int stagger;          // linear-tile kernel: the workgroup in the CU's second wave slot starts this many x 1024 cycles late
+    int early_refill;     // linear-tile kernel: the next chunk's input span is requested under the MFMAs of the chunk's last K-step
+                          // instead of after it (set by the kernel's own launcher from alink_debug_set_early_refill)
     int ablate;           // diagnostic timing-only modes of conv3x3_direct (0 = normal)
     // ALINK_DT_F16X2 only (powers of two, exact): stored value = true value x 2^e, e per tensor.
     float acc_scale;      // 2^(e_out - e_in - e_w): accumulator -> output units

@@ -36,6 +36,14 @@ constexpr int GPX = 224;        // pixels per workgroup: 14 tiles
 constexpr int TPW = 7;          // tiles per wave group (2 groups)
 constexpr int NT = 256;         // 4 waves: 2 pixel groups x 2 channel groups
 
+// s_waitcnt lgkmcnt(0), then the workgroup barrier, with a K-step's input fragments (both k-halves) as inputs: the LDS reads that
+// fill them cannot sink below the statement, and no LDS access or DMA moves across it (memory clobber).  vmcnt is left alone.
+template <typename V>
+__device__ __forceinline__ void reads_back_then_barrier(const V (&p0)[TPW], const V (&p1)[TPW]) {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::"v"(p0[0]), "v"(p0[1]), "v"(p0[2]), "v"(p0[3]), "v"(p0[4]), "v"(p0[5]), "v"(p0[6]),
+                 "v"(p1[0]), "v"(p1[1]), "v"(p1[2]), "v"(p1[3]), "v"(p1[4]), "v"(p1[5]), "v"(p1[6]) : "memory");
+}
+
 template <int W, int TCW>
 struct Lin {
     static constexpr int BN = 2 * TCW * 16;
@@ -231,10 +239,32 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
     wait_then_barrier<0>();
     if (stamps && tid == 0) stamps[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memtime();
 
+    // The single X buffer is refilled between chunks (SP: also between a chunk's hi and lo halves).  EARLY form (ConvParams::
+    // early_refill, the default; every instantiation, split precision included): the refill is requested INSIDE the chunk's
+    // last K-step.  That step reads the input fragments of BOTH k-halves first (14 x 4 registers, with the first half's weight
+    // fragments 72: what the other steps hold at their peak); once every wave's reads have returned the span is dead, while all
+    // 56 MFMAs of the step still run from registers — the DMA flies under them (the second half's weight fragments are read
+    // meanwhile, from a buffer the DMA does not touch) and the K-step's usual closing wait covers it.  The LATE form refills
+    // after the step, with nothing else in flight: in a launch that fills every slot at once the CU's two workgroups run in
+    // lockstep, so the co-resident one does not cover that wait.  Same MFMAs on the same operands, each accumulator's in the
+    // same order: bit-identical (tests/test_gpu_linear_refill.py).
+    const int early_form = p.early_refill;
     int wtog = 0;
     for (int cc = 0; cc < ncc; ++cc) {
 #pragma unroll 1
       for (int ph = 0; ph < NPH; ++ph) {
+        // SP: the hi half serves phases 0 and 1, the lo half phase 2
+        const bool next_chunk = ph == NPH - 1;
+        const bool refill = next_chunk ? cc + 1 < ncc : ph == 1;
+        const bool early = early_form != 0 && refill;
+        auto refill_x = [&]() {
+            // the chunk index is made opaque HERE, inside the (conditional) refill: otherwise the per-slot source addresses of
+            // the next span are formed ahead of the early form's block and held in 16 registers through the K-step's MFMAs
+            // (SP: stage_x makes its whole address arithmetic opaque already)
+            int cn = next_chunk ? cc_first + cc + 1 : cc_first + cc;
+            if (!SP) asm volatile("" : "+s"(cn));
+            stage_x(cn, next_chunk ? 0 : 1);
+        };
         auto step = [&](auto tapc) {
             constexpr int tap = decltype(tapc)::a;
             constexpr int ky = tap / 3, kx = tap % 3;
@@ -253,36 +283,75 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
             const int spos = sdl + ky * W + kx;
             const int xt0 = xbase + spos * 128 + ((q ^ ((spos >> 1) & 7)) << 4);
             const int xt1 = xt0 ^ 64;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                vec8 wf[TCW], pf[TPW];
+            auto frags_w = [&](int ks, vec8 (&wf)[TCW]) {
 #pragma unroll
                 for (int tt = 0; tt < TCW; ++tt) wf[tt] = *(const vec8*)(smem + (wl[ks] + wtog) + tt * 2048);
+            };
+            auto frags_x = [&](int ks, vec8 (&pf)[TPW]) {
 #pragma unroll
                 for (int u = 0; u < TPW; ++u) {
                     const unsigned t = tapbits ? (bnow & (tapbits << (4 * u))) : 0u;
                     const unsigned far = 4 * u < 18 ? t << (18 - (4 * u < 18 ? 4 * u : 0)) : t;
                     pf[u] = *(const vec8*)(smem + ((ks ? xt1 : xt0) + (int)far) + 2048 * u);
                 }
+            };
+            auto mfmas = [&](const vec8 (&wf)[TCW], const vec8 (&pf)[TPW], int u0, int u1) {      // tiles u0 .. u1 - 1
 #pragma unroll
                 for (int tt = 0; tt < TCW; ++tt)
 #pragma unroll
-                    for (int u = 0; u < TPW; ++u) acc[tt][u] = mfma16<T>(wf[tt], pf[u], acc[tt][u]);
+                    for (int u = u0; u < u1; ++u) acc[tt][u] = mfma16<T>(wf[tt], pf[u], acc[tt][u]);
+            };
+            if constexpr (tap == 8) {
+                // The chunk's last K-step, with the refill inside it.  One instruction stream for both forms — as two
+                // copies of the step behind a branch the compiler hoisted their common fragment reads above it and
+                // spilled them (300 bytes of scratch per lane in every 128-channel form) — with only the wait, the
+                // barrier and the DMA issue under the (workgroup-uniform) condition.  The schedule is pinned
+                // (sched_barrier): left free, the scheduler kept both halves' weight fragments beside the input
+                // fragments (88 registers) and the refill's addresses beside both, again into scratch.
+                vec8 wf0[TCW], pf0[TPW], wf1[TCW], pf1[TPW];
+                frags_w(0, wf0);
+                frags_x(0, pf0);
+                frags_x(1, pf1);
+                __builtin_amdgcn_sched_barrier(0);
+                if (early) {
+                    // the write-after-read rule of wait_then_barrier (conv_device.h) for the X span: every wave's reads of
+                    // it have RETURNED (the fragments are the statement's inputs, so no read sinks below it) before any
+                    // wave's DMA may overwrite it.  vmcnt is not waited on: the next step's weight DMA keeps flying.
+                    // (the previous step's MFMAs, which the compiler sinks below that step's barrier, run under this wait)
+                    const unsigned long long t0 = stamps ? __builtin_amdgcn_s_memtime() : 0ull;
+                    reads_back_then_barrier(pf0, pf1);
+                    if (stamps) refill_cycles += __builtin_amdgcn_s_memtime() - t0;
+                    refill_x();
+                }
+                mfmas(wf0, pf0, 0, 4);
+                __builtin_amdgcn_sched_barrier(0);
+                frags_w(1, wf1);
+                __builtin_amdgcn_sched_barrier(0);
+                mfmas(wf0, pf0, 4, TPW);
+                mfmas(wf1, pf1, 0, TPW);
+                // ... and the MFMAs stay ABOVE the closing wait: left alone the compiler sinks nearly all of the second half's
+                // below it (they carry no memory dependence), and the wave would sit out the DMA's flight with nothing issued
+                __builtin_amdgcn_sched_barrier(0);
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    vec8 wf[TCW], pf[TPW];
+                    frags_w(ks, wf);
+                    frags_x(ks, pf);
+                    mfmas(wf, pf, 0, TPW);
+                }
             }
-            wait_then_barrier<0>();      // end of the K-step: nothing stays in flight (the next step's weights have landed)
+            wait_then_barrier<0>();      // end of the K-step: nothing stays in flight (the next step's weights, and in the early
+                                         // form the next input span, have landed)
             wtog ^= WBYTES;
         };
         step(IC<0>{}); step(IC<1>{}); step(IC<2>{});
         step(IC<3>{}); step(IC<4>{}); step(IC<5>{});
         step(IC<6>{}); step(IC<7>{}); step(IC<8>{});
-        // SP: the hi half serves phases 0 and 1, the lo half phase 2
-        const bool next_chunk = ph == NPH - 1;
-        if (next_chunk ? cc + 1 < ncc : ph == 1) {
-            // single X buffer: every wave is past its last read of this chunk; refill and wait — the
-            // co-resident workgroup keeps the matrix cores busy meanwhile
+        if (refill && !early) {
+            // the late form: every wave is past its last read of this chunk; refill and wait, nothing else in flight
             const unsigned long long t0 = stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-            if (next_chunk) stage_x(cc_first + cc + 1, 0);
-            else            stage_x(cc_first + cc, 1);
+            refill_x();
             wait_then_barrier<0>();
             if (stamps) refill_cycles += __builtin_amdgcn_s_memtime() - t0;
         }
@@ -481,10 +550,13 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_linear_kernel(const ConvParams 
 }
 
 bool g_generic_epilogue = false;      // A/B: every launch on the run-time-flag epilogue (EPI = 0)
+int g_early_refill = 1;               // A/B: 0 = the input span refilled after the chunk's last K-step, not inside it
 
 template <typename T, int W, int TCW, bool SP = false>
-hipError_t launch_one(const ConvParams& p, hipStream_t st) {
+hipError_t launch_one(const ConvParams& p_in, hipStream_t st) {
     typedef Lin<W, TCW> G;
+    ConvParams p = p_in;
+    p.early_refill = g_early_refill;
     const long long totpix = (long long)p.N * p.H * W;
     const long long groups = (totpix + GPX - 1) / GPX;
     const long long nwg = groups * (p.Cout / G::BN);
@@ -558,6 +630,7 @@ int g_linear_mode = 31;
 
 extern "C" void alink_debug_set_linear(int mode) { g_linear_mode = mode; }
 extern "C" void alink_debug_set_generic_epilogue(int on) { g_generic_epilogue = on != 0; }
+extern "C" void alink_debug_set_early_refill(int on) { g_early_refill = on != 0 ? 1 : 0; }
 
 // Hardware contract probe: a DS read whose address lies beyond the workgroup's LDS allocation returns zero
 // (and does not fault).  The kernel above adds border bits 18..21 (tiles 0-4), 20..23 (tile 5) or 24..27 (tile 6)

@@ -58,6 +58,9 @@ void alink_debug_set_latency_form(int max_pixels);
 void alink_debug_set_latency_tiles(int form);
 /* start delay (x 1024 cycles) of the second workgroup on a CU in the linear-tile kernel (default 0; measured out) */
 void alink_debug_set_stagger(int n);
+/* 0: the linear-tile kernel refills its single input buffer after a 64-channel chunk's last K-step and waits with nothing
+ * else in flight (default 1: the refill is requested inside that K-step, under its MFMAs) */
+void alink_debug_set_early_refill(int on);
 /* in-call shards start one after the other's front (default 0; measured out) */
 void alink_debug_set_shard_stagger(int on);
 

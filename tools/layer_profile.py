@@ -27,6 +27,7 @@ ap.add_argument("--no-fuse-sc", action="store_true", help="A/B: projection short
 ap.add_argument("--no-fuse-unit", action="store_true", help="A/B: plain stage-1 units as two linear-tile launches instead of one (unit_c64.hip)")
 ap.add_argument("--no-fuse-unit1", action="store_true", help="A/B: stem + stage1_unit1 as the fused front kernel + the direct stride-2 kernel instead of one launch (unit1_c64.hip)")
 ap.add_argument("--linear", type=int, default=-1, help="linear-tile widths: bit0 56, bit1 28, bit2 14, bit3 7 (default: library default)")
+ap.add_argument("--late-refill", action="store_true", help="A/B: the linear-tile kernel refills its input span after a chunk's last K-step instead of inside it")
 a = ap.parse_args()
 units = W.ARCH_UNITS[a.model]
 from a_link_amd import _abi
@@ -40,6 +41,8 @@ if a.no_pair:
     _lib.alink_debug_set_pair(0)
 if a.linear >= 0:
     _lib.alink_debug_set_linear(a.linear)
+if a.late_refill:
+    _lib.alink_debug_set_early_refill(0)
 if a.no_fuse_sc:
     _lib.alink_debug_set_fuse_shortcut(0)
 if a.no_fuse_unit:

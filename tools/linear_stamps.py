@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Per-workgroup s_memtime timeline of one conv3x3_linear launch (the stamps are skipped by every product call:
-ConvParams::stamps is null there): where a workgroup's cycles go — prologue, main loop (with the time inside the
-single-buffered input refills), epilogue — and how the workgroups of a launch line up."""
+ConvParams::stamps is null there): where a workgroup's cycles go — prologue, main loop, epilogue — and how the workgroups of a
+launch line up.  The "refills" figure is what the single-buffered input refills still cost inside the main loop: with the early
+refill (the default) the cycles from entering the wait at the head of a chunk's last K-step — every wave's input fragment reads
+back — to leaving its barrier, the DMA itself flying under the step's MFMAs; with --late-refill (alink_debug_set_early_refill(0))
+the whole request-wait-barrier after the step, as before.  Compare the LOOP figures of the two forms, not the refill figures."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -10,7 +13,10 @@ from a_link_amd import _abi
 lib = _abi.init(0)
 lib.alink_debug_set_stamps.argtypes = [C.c_void_p]
 shapes = {"s3": (292, 14, 14, 256, 256), "s2": (292, 28, 28, 128, 128), "s4": (292, 7, 7, 512, 512), "s1": (292, 56, 56, 64, 64)}
-for name in sys.argv[1:] or ["s3", "s2", "s4", "s1"]:
+args = [a for a in sys.argv[1:] if a != "--late-refill"]
+if "--late-refill" in sys.argv[1:]:
+    lib.alink_debug_set_early_refill(0)
+for name in args or ["s3", "s2", "s4", "s1"]:
     N, H, W, Ci, Co = shapes[name]
     x = torch.randn(N, H, W, Ci, device="cuda").bfloat16()
     w = (torch.randn(Co, 3, 3, Ci, device="cuda") * 0.03).bfloat16()

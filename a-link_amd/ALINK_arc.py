@@ -27,6 +27,9 @@ def build_parser():
     p.add_argument("--grad_dtype", default="bf16", choices=["bf16", "f16"],
                    help="storage type of the input-gradient pass that --noise fgsm / pgd run through (an extension)")
     p.add_argument("--pretrain_steps", type=int, default=320000, help="n_steps of customTrainModel (code/siamese.py:81)")
+    p.add_argument("--face_boxes", default=None, metavar="FILE",
+                   help="DFW's face-coordinate file (Training_data_face_coordinate.txt): crop every photo to its box at load, for "
+                        "a dataset that is still whole photos (the reference crops the files in place beforehand)")
     p.add_argument("--quiet", action="store_true")
     return p
 
@@ -43,8 +46,10 @@ def main(argv=None):
     else:
         IMAGERES, FEATURERES, col = (224, 224), (2048,), 1
         conversionModel = siamese.RESNET50(IMAGERES, weights=FLAGS.resnet50_weights, grad_dtype=grad_dtype)
-    (X_plain, X_dig, X_imp) = readDFW.getAllTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES, conversionModel)
-    (X_plain_raw, X_dig_raw) = readDFW.getRawTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES)
+    faceBoxes = readDFW.constructIndexMap(FLAGS.face_boxes) if FLAGS.face_boxes else None
+    (X_plain, X_dig, X_imp) = readDFW.getAllTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES, conversionModel,
+                                                      faceBoxes=faceBoxes)
+    (X_plain_raw, X_dig_raw) = readDFW.getRawTrainData(FLAGS.dataDirPrefix, FLAGS.trainImagesDir, IMAGERES, faceBoxes=faceBoxes)
     assert 0 <= FLAGS.split_ratio <= 1 and 0 <= FLAGS.disparity_ratio <= 1 and 0 <= FLAGS.eps < 0.5
     noises = FLAGS.noise.split(',')
     if IMAGERES[0] % 56 == 0 and IMAGERES[0] // 32 * 32 != IMAGERES[0] and 'perlin' in noises:

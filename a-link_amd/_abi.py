@@ -37,6 +37,12 @@ class Gemm32Desc(C.Structure):
                 + [(n, _i) for n in ("relu", "accumulate", "splitk", "kper", "force_bk")])
 
 
+class IngestDesc(C.Structure):
+    """AlinkIngestDesc (include/alink_hip.h)"""
+    _fields_ = [("offset", _i64), ("H", C.c_int32), ("W", C.c_int32), ("mode", C.c_int32), ("box", C.c_int32 * 4),
+                ("m", C.c_double * 6)]
+
+
 _u64 = C.c_uint64
 _fp = C.POINTER(C.c_float)
 
@@ -167,6 +173,7 @@ PROTOTYPES = {
     "alink_perturb_images_multi": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_perturb_resize_multi": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_affine_warp": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "alink_ingest_faces": (_i, [_vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "alink_arcface_margin_workspace_bytes": (_sz, [_i, _i, _i]),
     "alink_arcface_margin_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "alink_contrastive_loss": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp, _vp]),

@@ -2,7 +2,7 @@
 
     get_model(ctx, image_size, model_str, layer)   code/face_model.py:28-41
     FaceModel(args)                                code/face_model.py:43-57
-    FaceModel.get_input(face_img)                  code/face_model.py:70-84  (HWC -> CHW only)
+    FaceModel.get_input(face_img, bbox, landmark)  code/face_model.py:70-84  (alignment when a box / landmarks are given, HWC -> CHW)
     FaceModel.get_feature(aligned)                 code/face_model.py:86-93  (forward + L2 normalise)
 
 Differences, all deliberate: the executor is batched (`get_features`), the checkpoint is the MXNet
@@ -59,7 +59,13 @@ class FaceModel(object):
         self.det_threshold = [0.6, 0.7, 0.8]
         self.image_size = image_size
 
-    def get_input(self, face_img):
+    def get_input(self, face_img, bbox=None, landmark=None):
+        """HWC -> CHW.  With a face box or five landmarks (from the caller's detector: none is built here) the photo is first
+        cropped / aligned to 112 x 112 by face_preprocess.preprocess — the call the reference wrote and commented out
+        (code/face_model.py:81), its DFW crops being cut beforehand."""
+        if bbox is not None or landmark is not None:
+            from . import face_preprocess
+            face_img = face_preprocess.preprocess(face_img, bbox, landmark, image_size='112,112')
         return np.transpose(face_img, (2, 0, 1))
 
     def get_feature(self, aligned):

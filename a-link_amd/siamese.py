@@ -611,3 +611,22 @@ class ArcFace:
         if len(X) == 0:
             return np.zeros((0, 512), dtype=np.float32)
         return self.model.get_features(X)
+
+    def process_raw(self, images, landmarks=None, bboxes=None):
+        """EXTENSION: whole photos, each (H, W, 3) of its own size -> (N, 512).  face_preprocess.preprocess_batch (landmarks:
+        alignment; boxes: crop with margin; neither: centre crop) on the model's device, then `process` on the device tensor —
+        the faces never visit the host — max_batch photos at a time."""
+        from . import face_preprocess
+        bb = self.model.model
+        n, size = len(images), self.model.image_size
+        if n == 0:
+            return np.zeros((0, 512), dtype=np.float32)
+        feats = []
+        for lo in range(0, n, bb.max_batch):
+            sl = slice(lo, lo + bb.max_batch)
+            faces = face_preprocess.preprocess_batch_device(images[sl], None if bboxes is None else bboxes[sl],
+                                                            None if landmarks is None else landmarks[sl], image_size=size,
+                                                            device=bb.device)
+            feats.append(self.process(faces))
+        import torch
+        return torch.cat(feats).cpu().numpy()

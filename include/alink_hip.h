@@ -703,6 +703,31 @@ int alink_perturb_resize_multi(const float* dev_imgs, const int* dev_img_of, int
  * source index outside [0, n_in) yields a row of NaN.  dev_out (n_out, H, W, C) must not overlap dev_in. */
 int alink_affine_warp(const float* dev_in, int n_in, const int32_t* dev_src, const double* dev_mat, const uint8_t* dev_copy,
                       int n_out, int H, int W, int C, int order, float* dev_out, void* stream);
+/* EXTENSION — the raw-photo front end (code/face_preprocess.py:46-111 — the call code/face_model.py:81 comments out — and the
+ * crop + resize of code/readDFW.py:28-62,82) for a RAGGED batch: n photos, each of its own size, become n faces of Ho x Wo in
+ * one launch.  dev_pixels is one packed table of total_elems elements (src_dtype 0: uint8, 1: float32) holding HWC photos end
+ * to end; descriptor i places photo i in it and names its route: */
+typedef struct AlinkIngestDesc {
+    int64_t offset;   /* first element of the photo in the table */
+    int32_t H, W;     /* its size; it occupies H * W * C elements */
+    int32_t mode;     /* 0: crop `box`, then resize;  1: affine warp by `m` */
+    int32_t box[4];   /* mode 0: x0, y0, x1, y1, half-open, inside the image */
+    double m[6];      /* mode 1: OUTPUT pixel (ox, oy) -> source (sx, sy) = ((ox m0 + oy m1) + m2, (ox m3 + oy m4) + m5) */
+} AlinkIngestDesc;
+/*   mode 0: what alink_resize_bilinear gives for the sub-image `box` resized to (Ho, Wo), bit for bit — the same tap rule and
+ *           roundings (csrc/resize_taps.h) relative to the box; no tap leaves the box.
+ *   mode 1: bilinear interpolation at (sx, sy) with a black border, in float64 with scipy's operation order: per axis
+ *           w0 = 1 - (s - floor s), w1 = 1 - w0; t = 0 + sum over the 2 x 2 taps (row-major) of (v * wy) * wx with v = 0 for a
+ *           tap outside the image; exactly 0 when sx <= -1, sx >= W, sy <= -1 or sy >= H; out = (float) t.  Equal bit for bit
+ *           to scipy.ndimage.affine_transform(channel, [[m4, m3], [m1, m0]], offset=[m5, m2], output_shape=(Ho, Wo), order=1,
+ *           mode='grid-constant', cval=0, output=float32).
+ * dev_out is (n, Ho, Wo, C) for layout 0 (NHWC) or (n, C, Ho, Wo) for layout 1 (NCHW), float32, unrounded.  The kernel never
+ * reads outside the table: a descriptor with offset < 0, offset + H W C > total_elems, H or W < 1, an unknown mode or, in
+ * mode 0, a box that is empty or leaves the image yields a row of NaN (callers validate on the host: a-link_amd/
+ * face_preprocess.py).  ALINK_EINVAL: C, Ho, Wo < 1, an unknown layout or src_dtype, 2^31 or more workgroups
+ * (n * ceil(Ho Wo / 256)), dev_out overlapping the table.  Runs on the device that owns dev_out. */
+int alink_ingest_faces(const void* dev_pixels, int src_dtype, int64_t total_elems, const AlinkIngestDesc* dev_desc, int n, int C,
+                       int Ho, int Wo, int layout, float* dev_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * EXTENSIONS — named by BASELINE.json's north_star, ABSENT from the reference: the reference

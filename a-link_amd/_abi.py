@@ -182,6 +182,8 @@ PROTOTYPES = {
     "alink_topk_scratch_bytes": (_sz, [_i64, _i]),
     "alink_topk": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "alink_identify_rows": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "alink_ranked_batch_scratch_bytes": (_sz, [_i64, _i]),
+    "alink_ranked_batch": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -76,6 +76,26 @@ class Bagging:
         probs = _head.committee_member_probs_device(hs, emb_left, emb_right, li, ri)
         return _dis.score_members_device(probs, want=(kind,))[kind]
 
+    def ranked_batch_indexed(self, emb_left, emb_right, li, ri, labeled, n_instances, kind="entropy", alpha=None):
+        """Extension: a ranked batch (batch.py; modAL.batch) of n_instances among the pairs (li[p], ri[p]) gathered from ONE
+        left and ONE right embedding matrix on device — the utility weighed against each pair's distance, as the row
+        |left - right|, to the labelled rows `labeled` (M, D) and to the picks so far, so near-duplicate pairs do not fill
+        the batch.  `kind`: "uncertainty" / "entropy" of predict_indexed's mean (uncertainty.score_device), or a kind of
+        disagreement_indexed; "margin" is refused (a SMALLER margin is the more uncertain).  -> (idx int32 (k,), scores (k,))
+        on the device, batch.ranked_batch_device's.  Members behind their own feature extractors (lists of matrices) have no
+        single row space: score them with disagreement_indexed and call batch.ranked_batch_device on the rows of choice."""
+        from . import batch as _batch, disagreement as _dis, uncertainty as _unc
+        if isinstance(emb_left, (list, tuple)) or isinstance(emb_right, (list, tuple)):
+            raise ValueError("ranked_batch_indexed measures distances in one feature space: one left and one right matrix, not one per member")
+        if kind in ("uncertainty", "entropy"):
+            utility = _unc.score_device(self.predict_indexed(emb_left, emb_right, li, ri), kind)
+        elif kind in _dis.KINDS:
+            utility = self.disagreement_indexed(emb_left, emb_right, li, ri, kind=kind)
+        else:
+            raise ValueError("unknown utility kind %r: choose among %s (margin: smaller is more uncertain, so it cannot weigh "
+                             "against a distance)" % (kind, ["uncertainty", "entropy"] + list(_dis.KINDS)))
+        return _batch.ranked_batch_device((emb_left, emb_right, li, ri), utility, labeled, n_instances, alpha=alpha)
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

@@ -585,6 +585,33 @@ int alink_committee_disagreement(const float* const* dev_member_probs, int n_mem
 size_t alink_topk_scratch_bytes(int64_t P, int k);
 int alink_topk(const float* dev_scores, int64_t P, int k, int largest, int32_t* dev_idx,
                float* dev_vals, void* dev_scratch, void* stream);
+/* Ranked batch-mode query selection (modAL.batch: Cardoso et al. 2017), the greedy rule that keeps a batch from filling with
+ * near-duplicates: EXTENSION, no reference driver calls it.  N pool rows x_n of D floats, M labelled rows z_m (dev_labeled,
+ * (M, D), always materialised), a utility u_n per pool row (larger = more informative), a batch of k (clipped to N).
+ *   d2_n    = min over the labelled rows and the picks so far of |x_n - .|^2        (squared Euclidean distance)
+ *   for pick t = 0 .. k - 1:
+ *     alpha_t = (N - t) / (N + M)          |unlabelled| / (|unlabelled| + |labelled|), picks counting as labelled: the
+ *                                          float32 of the float64 quotient; a caller's alpha in [0, 1] replaces it
+ *     score_n = alpha_t (1 - 1 / (1 + sqrt(d2_n))) + (1 - alpha_t) u_n              for every row not yet picked
+ *     pick_t  = argmax_n score_n, ties to the lower index;  d2_n = min(d2_n, |x_n - x_pick|^2)
+ * dev_idx[t] = pick_t in order, dev_scores[t] = the score it had when picked.  `>` comparisons: a NaN score never wins, and
+ * once nothing but NaN scores is left the remaining picks are -1.
+ * Two row forms: dev_li == NULL: dev_x is the (N, D) row table (dev_r, dev_ri unused); otherwise row n is
+ * |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the fly from a left and a right feature table of D columns (the index form
+ * of alink_head_forward; what the pair scorer sees, code/siamese.py:27-35) — the N x D rows are never materialised, and the
+ * indices are NOT range-checked.
+ * Arithmetic is pinned: float32; the D squared differences are summed by fused multiply-add in one fixed order that depends
+ * on D alone (element e to lane (e / 4) % 64, ascending per lane, then an xor butterfly over the 64 lanes), the same in
+ * both row forms, so both give the same bits; sqrt and the division are correctly rounded; the score is
+ * fl(fl(alpha fl(1 - s)) + fl(fl(1 - alpha) u)) with s = fl(1 / fl(1 + fl(sqrt(d2)))), no product contracted into the sum.
+ * The call enqueues 1 + k + 1 launches on `stream` and returns: no host synchronisation, nothing read back.
+ * Limits (ALINK_EINVAL beyond): 1 <= N < 2^31, 1 <= D <= 8192 (the picked row is held in LDS), M >= 1 (the cold start — the
+ * row nearest to all others — is O(N^2 D) and stays on the host: a-link_amd/batch.py), k >= 1, alpha <= 1 (alpha < 0: the
+ * schedule).  dev_scratch >= alink_ranked_batch_scratch_bytes(N, k), 256-byte aligned. */
+size_t alink_ranked_batch_scratch_bytes(int64_t N, int k);
+int alink_ranked_batch(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                       const float* dev_labeled, int64_t M, const float* dev_utility, int k, float alpha, int32_t* dev_idx,
+                       float* dev_scores, void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

@@ -160,14 +160,13 @@ class _FeatureScorer(object):
         """16-bit storage only: did a forward of the lanes in flight leave the float16 range?  (The backbone checks this
         itself after every call by synchronising the device — here the flag is read once per step, after the step's
         own event, so that the other lane keeps the device busy.)  Split precision re-calibrates on the images in flight
-        (scales only go down), as IRBackbone._checked does, and the step is run again; plain f16 raises."""
+        (scales only go down), the rule of net_host.ImageNet._checked, and the step is run again; plain f16 raises."""
         ub = self.ub
         if ub.dtype in ("f16", "f16x2") and ub.range_left(reset=False):
-            if ub.dtype != "f16x2":
-                eng.torch.cuda.synchronize(eng.device)
-                ub.range_left()
-                raise _abi.AlinkError("activations exceeded the float16 range in this network: build the backbone with dtype='bf16'")
-            self._recalibrate(eng)
+            if ub.dtype == "f16x2":
+                self._recalibrate(eng)
+            else:
+                ub.check_range()                     # synchronises, clears the flag and raises
 
     def recover(self, eng):
         """an enqueue raised: the other lane's forward raised the range flag while this one was being enqueued (the backbone

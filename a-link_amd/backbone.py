@@ -10,21 +10,18 @@ import numpy as np
 
 from . import _abi
 from . import weights as W
+from .net_host import F16_STORAGE, ImageNet
 
 
-class IRBackbone(object):
+class IRBackbone(ImageNet):
+    prefix = "alink_backbone"
     DTYPES = {"bf16": _abi.DT_BF16, "f16": _abi.DT_F16, "f32": _abi.DT_F32, "f16x2": _abi.DT_F16X2}
 
     def __init__(self, params, image_size=(112, 112), emb=512, dtype="bf16", device=None, max_batch=292,
                  widths=W.WIDTHS, streams=2, shards_per_call=None, bn_eps=2e-5, enable_grad=False,
                  small_batch_split=False, lazy_range_check=False):
-        import torch
-        self.torch = torch
-        if not torch.cuda.is_available():
-            raise _abi.AlinkError("no ROCm device visible: a-link_amd computes only on the GPU (no CPU fallback)")
-        device = _abi.resolve_device(device)          # None: the current torch device
-        self.device = device
-        self.lib = _abi.init(device)
+        self.device = self._open(device)              # None: the current torch device
+        self._embed = self.lib.alink_embed
         self.units = W.infer_units(params)
         self.emb = emb
         self.image_size = tuple(image_size)
@@ -60,13 +57,10 @@ class IRBackbone(object):
             self.dtype = dt
             self._build(cfg, params, small_batch_split, enable_grad)
             if dt == "f16x2":
-                self._ws = {}
-                self.calibrate(self._probe_images())
+                self.calibrate(self.probe_images())
             if dtype != "auto" or dt == "bf16" or self._range_probe_ok():
                 break
-            self.lib.alink_backbone_destroy(self.h)
-            self.h = None
-            self._ws = {}
+            self._destroy()
         # shards_per_call: image shards ONE alink_embed call is split into on the library's internal streams.  None
         # (default) = 2 for a call that is alone on its stream and has >= 192 images — two half-launches de-phase each
         # other's prologue / epilogue bursts: IR-50, one 256-image batch per step 65.9k -> 72.0k embeddings/s, IR-100 at
@@ -81,55 +75,26 @@ class IRBackbone(object):
         self.n_streams = max(1, int(streams))
         self._side = None
         self._upload = None
-        self._ws = {}
+        self.ws.slots.clear()                         # the probe / calibration workspace of the build is not kept
 
     def _build(self, cfg, params, small_batch_split, enable_grad):
-        with _abi.on_device(self.device):             # the handle lives on the device current at create
-            self.h = self.lib.alink_backbone_create(C.byref(cfg))
-        if not self.h:
-            raise _abi.AlinkError("alink_backbone_create: " + self.lib.alink_last_error().decode())
+        self._create(self.device, C.byref(cfg))
         if small_batch_split:      # latency mode: batches <= 32 split their convolutions over K (not bit-equal to fused)
             _abi.check(self.lib.alink_backbone_set_small_batch_split(self.h, 1), "alink_backbone_set_small_batch_split")
         if enable_grad:
             _abi.check(self.lib.alink_backbone_enable_grad(self.h), "alink_backbone_enable_grad")
-        n = self.lib.alink_backbone_num_tensors(self.h)
-        name, cnt = C.c_char_p(), C.c_size_t()
-        for i in range(n):
-            _abi.check(self.lib.alink_backbone_tensor_info(self.h, i, C.byref(name), C.byref(cnt)))
-            key = name.value.decode()
-            if key not in params:
-                raise KeyError("checkpoint is missing tensor %s" % key)
-            a = np.ascontiguousarray(params[key], dtype=np.float32)
-            _abi.check(self.lib.alink_backbone_load(self.h, name.value, _abi.ptr(a), a.size), "load " + key)
-        _abi.check(self.lib.alink_backbone_finalize(self.h), "alink_backbone_finalize")
+        self.load_tensors(params, "checkpoint is")
         self._shards_now = None                       # a new handle: its shard count is not set yet
-
-    def _probe_images(self):
-        torch = self.torch
-        h, w = self.image_size
-        g = torch.Generator(device="cpu").manual_seed(0)
-        return torch.stack([torch.randint(0, 256, (h, w, 3), generator=g).float(), torch.zeros(h, w, 3),
-                            torch.full((h, w, 3), 255.0)]).to("cuda:%d" % self.device)
 
     def calibrate(self, x, merge=False):
         """dtype 'f16x2': choose the per-tensor power-of-two scales from these images (CUDA tensor or host array in any
         accepted layout; ALL of them, max_batch at a time: the first chunk sets the scales unless merge, every further
         chunk only lowers them).  merge=True only ever lowers a scale.  Embeddings are bit-reproducible for FIXED
         scales: share them with state() / load_state() (checkpoints, the ranks of a job)."""
-        if self.dtype != "f16x2":
-            raise _abi.AlinkError("only dtype='f16x2' is calibrated")
-        torch = self.torch
         if isinstance(x, np.ndarray):
-            x = torch.from_numpy(np.ascontiguousarray(x if x.dtype == np.uint8 else x.astype(np.float32)))
-        layout = self._layout_of(x, self.image_size)
-        for i in range(0, x.shape[0], self.max_batch):
-            xc = x[i:i + self.max_batch].to("cuda:%d" % self.device).contiguous()
-            n = xc.shape[0]
-            ws, wsb = self._workspace(n)
-            torch.cuda.synchronize(self.device)
-            _abi.check(self.lib.alink_backbone_calibrate(self.h, _abi.ptr(xc), layout, n, C.c_void_p(ws), wsb,
-                                                         1 if (merge or i) else 0, _abi.current_stream(self.device)),
-                       "alink_backbone_calibrate")
+            x = self.torch.from_numpy(np.ascontiguousarray(x if x.dtype == np.uint8 else x.astype(np.float32)))
+        layout, fn = self._layout_of(x, self.image_size), self.lib.alink_backbone_calibrate
+        self._calibrate_chunks(x, merge, lambda xc, n, ws, wsb, m, st: fn(self.h, _abi.ptr(xc), layout, n, ws, wsb, m, st))
 
     def set_products(self, n):
         """dtype 'f16x2': matrix-core products per multiplication for the launches that follow — 3 = the exact mode
@@ -145,35 +110,18 @@ class IRBackbone(object):
             raise _abi.AlinkError("screening_view is the one-product form of dtype='f16x2'")
         return _ScreeningView(self)
 
-    def state(self):
-        """The calibration state of the split-precision mode as a small dict of plain ints ({} for any other dtype): what
-        has to travel with a checkpoint, and from the rank that calibrated to every other rank, for embeddings to be
-        bit-identical there (include/alink_hip.h: alink_backbone_get_scales)."""
-        n = self.lib.alink_backbone_num_scales(self.h)
-        if n == 0:
-            return {}
-        e = (C.c_int * n)()
-        _abi.check(self.lib.alink_backbone_get_scales(self.h, e, n), "alink_backbone_get_scales")
-        return {"dtype": self.dtype, "units": [int(u) for u in self.units], "image_size": [int(v) for v in self.image_size],
-                "scale_exponents": [int(v) for v in e]}
+    def _identity(self):
+        return {"units": [int(u) for u in self.units], "image_size": [int(v) for v in self.image_size]}
 
-    def load_state(self, st):
-        """Install scales saved by state() (same architecture and image size)."""
-        if not st:
-            return
-        if st.get("dtype") != self.dtype or list(st.get("units", [])) != [int(u) for u in self.units] or \
-                list(st.get("image_size", [])) != [int(v) for v in self.image_size]:
-            raise _abi.AlinkError("calibration state of a %s %s network at %s does not fit this %s %s network at %s"
-                                  % (st.get("dtype"), st.get("units"), st.get("image_size"), self.dtype, list(self.units), list(self.image_size)))
-        v = [int(x) for x in st["scale_exponents"]]
-        e = (C.c_int * len(v))(*v)
-        _abi.check(self.lib.alink_backbone_set_scales(self.h, e, len(v)), "alink_backbone_set_scales")
+    def _misfit(self, st):
+        return ("calibration state of a %s %s network at %s does not fit this %s %s network at %s"
+                % (st.get("dtype"), st.get("units"), st.get("image_size"), self.dtype, list(self.units), list(self.image_size)))
 
     def _range_probe_ok(self):
         torch = self.torch
-        x = self._probe_images()
+        x = self.probe_images()
         saved, self.dtype = self.dtype, "probe"       # _checked must not raise here
-        self._ws, self._side, self._upload, self.n_streams = {}, None, None, 1
+        self._side, self._upload, self.n_streams = None, None, 1
         out = self.embed_device(x)
         self.dtype = saved
         return bool(torch.isfinite(out).all())
@@ -182,25 +130,6 @@ class IRBackbone(object):
         if n != self._shards_now:
             _abi.check(self.lib.alink_backbone_set_streams(self.h, int(n)), "alink_backbone_set_streams")
             self._shards_now = n
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.alink_backbone_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    # -- workspace -------------------------------------------------------------------------------
-    def _workspace(self, n, slot=0):
-        cur = self._ws.get(slot)
-        if cur is None or n > cur[1]:
-            nbytes = self.lib.alink_backbone_workspace_bytes(self.h, n)
-            cur = (self.torch.empty(nbytes + 256, dtype=self.torch.uint8, device="cuda:%d" % self.device), n)
-            self._ws[slot] = cur
-        t = cur[0]
-        off = (-t.data_ptr()) % 256
-        return t.data_ptr() + off, t.numel() - off
 
     @staticmethod
     def _layout_of(x, image_size):
@@ -214,40 +143,14 @@ class IRBackbone(object):
             return _abi.LAYOUT_NCHW_F32
         raise ValueError("images of shape %s do not match (N,%d,%d,3) / (N,3,%d,%d)" % (tuple(x.shape), h, w, h, w))
 
-    def range_left(self, reset=True):
-        """True if, since the last reset, some embedding came out non-finite (float16 storage has 5 exponent bits).  The
-        flag is one word of pinned host memory that the last kernel of a forward writes: synchronise first."""
-        return bool(self.lib.alink_backbone_range_flag(self.h, 1 if reset else 0))
-
-    def check_range(self):
-        """Synchronise this device and raise if a float16-storage forward left the range since the last check."""
-        if self.dtype in ("f16", "f16x2"):
-            self.torch.cuda.synchronize(self.device)
-            if self.range_left():
-                raise _abi.AlinkError("activations exceeded the float16 range in this network: build the backbone with "
-                                      "dtype='bf16' (or, for dtype='f16x2', calibrate() on images like these)")
-
-    def _checked(self, out, redo=None):
-        """float16 storage: a network whose activations leave +-65504 (deep nets with synthetic weights do) comes out as
-        NaN.  Fail loudly instead of returning it (bf16 has the range).  The test is a flag the FC-finish kernel raises,
-        read after ONE synchronisation per call — or, with lazy_range_check, only in check_range() and at the start of
-        the next call.  Split precision re-calibrates on the offending batch (scales only go down) and re-runs once."""
-        if self.dtype not in ("f16", "f16x2") or self.lazy_range_check:
-            return out
-        self.torch.cuda.synchronize(self.device)
-        if self.range_left():
-            if self.dtype == "f16x2" and redo is not None:
-                self.calibrate(redo, merge=True)
-                out = self.embed_device(redo, out=out, _retry=False)
-                return out
-            raise _abi.AlinkError("activations exceeded the float16 range in this network: build the backbone with dtype='bf16'")
-        return out
+    def _check_input(self, x):
+        return self._layout_of(x, self.image_size)
 
     def embed_device(self, x, out=None, _retry=True):
         """x: CUDA tensor (N,H,W,3) f32|u8 or (N,3,H,W) f32, contiguous.  Returns (N, emb) f32 CUDA."""
         torch = self.torch
         layout = self._layout_of(x, self.image_size)
-        if self.lazy_range_check and self.dtype in ("f16", "f16x2") and self.range_left(reset=False):
+        if self.lazy_range_check and self.dtype in F16_STORAGE and self.range_left(reset=False):
             self.range_left()
             raise _abi.AlinkError("an earlier forward left the float16 range (lazy_range_check): its embeddings are not finite")
         if not x.is_contiguous():
@@ -261,9 +164,8 @@ class IRBackbone(object):
             for i in range(0, n, self.max_batch):
                 m = min(self.max_batch, n - i)
                 self._set_shards(self._shards_fixed or (2 if m >= 192 else 1))
-                ws, wsb = self._workspace(m)
-                _abi.check(self.lib.alink_embed(self.h, _abi.ptr(x[i:i + m]), layout, m, _abi.ptr(out[i:i + m]),
-                                                C.c_void_p(ws), wsb, st), "alink_embed")
+                ws, wsb = self.ws.get(m)
+                _abi.check(self._embed(self.h, _abi.ptr(x[i:i + m]), layout, m, _abi.ptr(out[i:i + m]), ws, wsb, st), "alink_embed")
             return self._checked(out, x if _retry else None)
         if self._side is None:
             self._side = [torch.cuda.Stream(device=x.device) for _ in range(self.n_streams)]
@@ -277,10 +179,9 @@ class IRBackbone(object):
         for j, i in enumerate(range(0, n, self.max_batch)):
             m = min(self.max_batch, n - i)
             slot = j % used
-            ws, wsb = self._workspace(m, slot + 1)
-            _abi.check(self.lib.alink_embed(self.h, _abi.ptr(x[i:i + m]), layout, m, _abi.ptr(out[i:i + m]),
-                                            C.c_void_p(ws), wsb, C.c_void_p(self._side[slot].cuda_stream)),
-                       "alink_embed")
+            ws, wsb = self.ws.get(m, slot + 1)
+            _abi.check(self._embed(self.h, _abi.ptr(x[i:i + m]), layout, m, _abi.ptr(out[i:i + m]), ws, wsb,
+                                   self._side[slot].cuda_stream), "alink_embed")
         for s in self._side[:used]:
             done = torch.cuda.Event()
             done.record(s)
@@ -288,30 +189,10 @@ class IRBackbone(object):
         return self._checked(out, x if _retry else None)
 
     # -- input gradient (FGSM / PGD extension) --------------------------------------------------------
-    def _grad_workspace(self, n):
-        cur = self._ws.get("grad")
-        if cur is None or n > cur[1]:
-            nbytes = self.lib.alink_backbone_grad_workspace_bytes(self.h, n)
-            cur = (self.torch.empty(nbytes + 256, dtype=self.torch.uint8, device="cuda:%d" % self.device), n)
-            self._ws["grad"] = cur
-        t = cur[0]
-        off = (-t.data_ptr()) % 256
-        return t.data_ptr() + off, t.numel() - off
-
     def embed_with_cache(self, x):
         """Forward on <= max_batch images keeping what input_gradient needs.  x: CUDA float32 NHWC/NCHW."""
-        if not self.grad_enabled:
-            raise _abi.AlinkError("IRBackbone was built without enable_grad=True")
-        torch = self.torch
-        layout = self._layout_of(x, self.image_size)
-        if layout == _abi.LAYOUT_NHWC_U8:
-            raise ValueError("gradients need float32 pixels")
-        x = x.contiguous()
-        n = x.shape[0]
-        assert 0 < n <= self.max_batch
-        out = torch.empty((n, self.emb), dtype=torch.float32, device=x.device)
-        ws, wsb = self._grad_workspace(n)
-        _abi.check(self.lib.alink_embed_cached(self.h, _abi.ptr(x), layout, n, _abi.ptr(out), C.c_void_p(ws), wsb,
+        layout, x, n, out, ws, wsb = self._cache_args(x, self.emb)
+        _abi.check(self.lib.alink_embed_cached(self.h, _abi.ptr(x), layout, n, _abi.ptr(out), ws, wsb,
                                                _abi.current_stream(self.device)), "alink_embed_cached")
         self._cached = (n, layout, out)
         return out
@@ -319,16 +200,12 @@ class IRBackbone(object):
     def input_gradient(self, demb):
         """d(loss)/d(pixels) for the batch of the last embed_with_cache, given demb = d(loss)/d(embedding)
         (n, emb) float32 CUDA.  Same layout as the forward input."""
-        torch = self.torch
-        n, layout, emb = self._cached
-        demb = demb.to(torch.float32).contiguous()
-        assert tuple(demb.shape) == (n, self.emb)
+        (n, layout, emb), demb, ws, wsb = self._grad_args(demb, self.emb)
         h, w = self.image_size
         shape = (n, h, w, 3) if layout == _abi.LAYOUT_NHWC_F32 else (n, 3, h, w)
-        dpix = torch.empty(shape, dtype=torch.float32, device=demb.device)
-        ws, wsb = self._grad_workspace(n)
-        _abi.check(self.lib.alink_embed_input_grad(self.h, _abi.ptr(demb), _abi.ptr(emb), layout, n, _abi.ptr(dpix),
-                                                   C.c_void_p(ws), wsb, _abi.current_stream(self.device)), "alink_embed_input_grad")
+        dpix = self.torch.empty(shape, dtype=self.torch.float32, device=demb.device)
+        _abi.check(self.lib.alink_embed_input_grad(self.h, _abi.ptr(demb), _abi.ptr(emb), layout, n, _abi.ptr(dpix), ws, wsb,
+                                                   _abi.current_stream(self.device)), "alink_embed_input_grad")
         return dpix
 
     def embed(self, x):
@@ -369,13 +246,13 @@ class IRBackbone(object):
         n = x.shape[0]
         assert n <= self.max_batch
         out = torch.empty((n, self.emb), dtype=torch.float32, device=x.device)
-        ws, wsb = self._workspace(n)
+        ws, wsb = self.ws.get(n)
         cap = 1024
         ms = (C.c_float * cap)()
         fl = (C.c_double * cap)()
         kd = (C.c_int * cap)()
         nl = C.c_int(cap)
-        _abi.check(self.lib.alink_embed_profile(self.h, _abi.ptr(x), layout, n, _abi.ptr(out), C.c_void_p(ws), wsb,
+        _abi.check(self.lib.alink_embed_profile(self.h, _abi.ptr(x), layout, n, _abi.ptr(out), ws, wsb,
                                                 _abi.current_stream(self.device), ms, fl, kd, C.byref(nl)), "alink_embed_profile")
         return [(kd[i], ms[i], fl[i]) for i in range(nl.value)]
 

@@ -120,9 +120,8 @@ def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
     -> (idx int32 (k,), scores float32 (k,)) on the device: the picks in order and the score each had when picked; ties go
     to the lower index, a NaN utility never wins.  Nothing is synchronised or read back except, in the pair form, the
     range check of li / ri."""
-    import ctypes as C
     import torch
-    from . import _abi
+    from . import _abi, net_host
     if isinstance(rows, (tuple, list)):
         if len(rows) != 4:
             raise ValueError("rows: an (N, D) tensor or a tuple (left, right, li, ri)")
@@ -163,13 +162,11 @@ def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
         raise ValueError("n_instances = %r must be at least 1" % (n_instances,))
     lib = _abi.init(dev.index or 0)
     k = min(int(n_instances), N)
-    nb = lib.alink_ranked_batch_scratch_bytes(N, int(n_instances))
-    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    off = (-scratch.data_ptr()) % 256
+    scratch, sp, _ = net_host.aligned_scratch(lib.alink_ranked_batch_scratch_bytes(N, int(n_instances)), dev)
     idx = torch.empty(max(k, 0), dtype=torch.int32, device=dev)
     scores = torch.empty(max(k, 0), dtype=torch.float32, device=dev)
     _abi.check(lib.alink_ranked_batch(_abi.ptr(left), _abi.ptr(right), _abi.ptr(li), _abi.ptr(ri), N, D, _abi.ptr(labeled), M,
                                       _abi.ptr(utility), int(n_instances), -1.0 if alpha is None else float(alpha), _abi.ptr(idx),
-                                      _abi.ptr(scores), C.c_void_p(scratch.data_ptr() + off), _abi.current_stream(dev)),
+                                      _abi.ptr(scores), sp, _abi.current_stream(dev)),
                "alink_ranked_batch")
     return idx, scores

@@ -10,9 +10,7 @@ Labelled extensions like noise.FGSM / noise.PGD: nothing in the drop-in path use
 fine-tune the embedding space itself.  HIP kernels in csrc/margin.hip (exact-f32 MFMA GEMMs of csrc/sgemm.hip for the
 cosine matrix and its two gradient products); checked against torch autograd in tests/test_gpu_extensions.py.
 """
-import ctypes as C
-
-from . import _abi
+from . import _abi, net_host
 
 
 def _device_of(x):
@@ -42,14 +40,13 @@ def arcface_margin_loss(emb, weight, labels, s=64.0, m=0.5, easy_margin=False, n
     if int(y.min()) < 0 or int(y.max()) >= c:
         raise ValueError("labels outside 0..%d" % (c - 1))
     nb = lib.alink_arcface_margin_workspace_bytes(n, d, c)
-    ws = torch.empty(nb + 256, dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws, wsp, _ = net_host.aligned_scratch(nb, dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     de = torch.empty_like(e) if need_grads else None
     dw = torch.empty_like(w) if need_grads else None
     _abi.check(lib.alink_arcface_margin_loss(_abi.ptr(e), _abi.ptr(w), _abi.ptr(y), n, d, c, float(s), float(m),
                                              1 if easy_margin else 0, _abi.ptr(loss), _abi.ptr(de), _abi.ptr(dw),
-                                             C.c_void_p(ws.data_ptr() + off), nb, _abi.current_stream(dev)),
+                                             wsp, nb, _abi.current_stream(dev)),
                "alink_arcface_margin_loss")
     return loss[0], de, dw
 

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from .net_host import Handle
 
 
 def glorot_uniform(rng, fan_in, fan_out):
@@ -159,19 +160,15 @@ def _evaluate(self, x, y, batch_size=32, verbose=0):
 KerasFitMixin.evaluate = _evaluate
 
 
-class DenseHead(KerasFitMixin):
+class DenseHead(KerasFitMixin, Handle):
     """abs(l - r) -> Dense(h1, relu) -> Dense(h2, relu) -> Dense(2) -> softmax; BCE + Adadelta.
     out_dim=1 is the baseline scripts' variant: Dense(1, sigmoid) (reference code/siamese3.py:25)."""
+    prefix = "alink_head"
 
     def __init__(self, d_in, h1=512, h2=64, lr=1.0, rho=0.95, eps=1e-8, seed=None, device=None, out_dim=2,
                  compute_dtype="f32"):
-        import torch
-        self.torch = torch
-        if not torch.cuda.is_available():
-            raise _abi.AlinkError("no ROCm device visible: a-link_amd computes only on the GPU (no CPU fallback)")
-        device = _abi.resolve_device(device)          # None: the current torch device
-        self.device = "cuda:%d" % device
-        self.lib = _abi.init(device)
+        device = self._open(device)                   # None: the current torch device
+        torch, self.device = self.torch, "cuda:%d" % device
         self.d_in, self.h1, self.h2, self.out_dim = int(d_in), int(h1), int(h2), int(out_dim)
         with _abi.on_device(device):                  # the handle lives on the device current at create
             self.h = self.lib.alink_head_create_ex(self.d_in, self.h1, self.h2, self.out_dim, lr, rho, eps)
@@ -194,14 +191,6 @@ class DenseHead(KerasFitMixin):
         self._metrics_host_ptr = self._metrics_host.data_ptr()
         self._tdev = torch.device(self.device)
         self._stage = {}          # persistent device tensors the host batches are copied into
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.alink_head_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
     def set_compute_dtype(self, compute_dtype):
         """"f32" (default; Keras' floatx, what the reference trains in) or "bf16": mixed precision — f32 master

@@ -526,7 +526,7 @@ class ArcFace:
                 from ._abi import AlinkError
                 cand = face_model.FaceModel(_Args(dict(args, dtype="f16")))
                 try:                                   # do the probe images (uniform noise, black, white) fit plain f16?
-                    cand.model.embed_device(cand.model._probe_images())
+                    cand.model.embed_device(cand.model.probe_images())
                     self._screen = cand
                 except AlinkError:
                     del cand

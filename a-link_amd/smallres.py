@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _abi
 from .head import KerasFitMixin, glorot_uniform
+from .net_host import Handle
 
 MAXN = 256
 _NO_CONTEXT = contextlib.nullcontext()
@@ -50,15 +51,12 @@ def identify_rows(scores, col=1, true_ids=None):
     return flat, best, rank
 
 
-class SmallResNet(KerasFitMixin):
+class SmallResNet(KerasFitMixin, Handle):
+    prefix = "alink_smallres"
+
     def __init__(self, image_shape, feat, lr=1.0, rho=0.95, eps=1e-8, seed=None, device=None, prescale=False):
-        import torch
-        self.torch = torch
-        if not torch.cuda.is_available():
-            raise _abi.AlinkError("no ROCm device visible: a-link_amd computes only on the GPU (no CPU fallback)")
-        device = _abi.resolve_device(device)          # None: the current torch device
-        self.device = "cuda:%d" % device
-        self.lib = _abi.init(device)
+        device = self._open(device)                   # None: the current torch device
+        torch, self.device = self.torch, "cuda:%d" % device
         self.H, self.W = int(image_shape[0]), int(image_shape[1])
         assert int(image_shape[2]) == 3
         self.feat = int(feat)
@@ -98,14 +96,6 @@ class SmallResNet(KerasFitMixin):
         self._pin = {}
         self.use_graph = False
         self.prescale = 1 if prescale else 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.lib.alink_smallres_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
 
     def _shapes(self):
         return [(3, 3, 3, 32), (32,), (3, 3, 32, 32), (32,), (3, 3, 32, 64), (64,), (3, 3, 64, 64), (64,),

@@ -120,19 +120,16 @@ def score_device(probs, kind, b=None, col=0):
 
 def topk_device(scores, k, largest=True):
     """indices (int32 CUDA) of the k largest/smallest scores, sorted, ties -> lower index."""
-    import ctypes as C
     import torch
-    from . import _abi
+    from . import _abi, net_host
     lib = _abi.init(scores.device.index or 0)
     scores = scores.contiguous()
     P = scores.numel()
-    nb = lib.alink_topk_scratch_bytes(P, int(k))
-    scratch = torch.empty(nb + 256, dtype=torch.uint8, device=scores.device)
-    off = (-scratch.data_ptr()) % 256
+    scratch, sp, _ = net_host.aligned_scratch(lib.alink_topk_scratch_bytes(P, int(k)), scores.device)
     idx = torch.empty(int(k), dtype=torch.int32, device=scores.device)
     vals = torch.empty(int(k), dtype=torch.float32, device=scores.device)
     _abi.check(lib.alink_topk(_abi.ptr(scores), P, int(k), 1 if largest else 0, _abi.ptr(idx), _abi.ptr(vals),
-                              C.c_void_p(scratch.data_ptr() + off), _abi.current_stream(scores.device)), "alink_topk")
+                              sp, _abi.current_stream(scores.device)), "alink_topk")
     return idx, vals
 
 

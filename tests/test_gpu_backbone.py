@@ -643,3 +643,37 @@ def test_l2_epilogue_equals_sklearn_normalize(gpu):
         assert np.abs(got - want).max() < tol, (dt, np.abs(got - want).max())
         np.testing.assert_allclose(preprocessing.normalize(got), got, rtol=0, atol=2e-7)     # already unit rows
         np.testing.assert_allclose(np.linalg.norm(got.astype(np.float64), axis=1), 1.0, atol=3e-7)
+
+
+def _grow_shrink_case(under_test, fresh, x, counts):
+    """The workspace cache under real growth: batches of counts[0], counts[1], counts[2] images (small, large, small) on ONE handle;
+    every row must equal, bit for bit, the same image embedded alone on a fresh handle (which never grows)."""
+    alone = torch.cat([fresh.embed_device(x[i:i + 1]) for i in range(len(x))])
+    first, grown, shrunk = counts
+    for lo, hi in ((0, first), (0, grown), (grown - shrunk, grown)):
+        got = under_test.embed_device(x[lo:hi])
+        assert torch.isfinite(got).all() and torch.equal(got, alone[lo:hi]), (lo, hi)
+
+
+def test_workspace_cache_grows_and_shrinks_on_one_handle(gpu):
+    """3 images (one chunk on the caller's stream), then 9 (three chunks of max_batch = 4 over two side streams, each with a
+    workspace slot of its own, the last one ragged), then 3 again on the grown buffers."""
+    from a_link_amd import weights as W
+    from a_link_amd.backbone import IRBackbone
+    size = (112, 112)
+    params = W.synthetic_ir_params((1, 1, 1, 1), size=size, seed=4)
+    x = torch.from_numpy(_pixels(9, size, seed=5)).cuda()
+    bb = IRBackbone(params, image_size=size, dtype="bf16", max_batch=4, streams=2)
+    _grow_shrink_case(bb, IRBackbone(params, image_size=size, dtype="bf16", max_batch=4, streams=2), x, (3, 9, 3))
+    assert sorted(bb.ws.slots) == [0, 1, 2]
+
+
+def test_workspace_cache_grows_and_shrinks_on_one_resnet50_handle(gpu):
+    """The same for VGGResNet50 at its smallest accepted size (197 x 197: the last map is 7 x 7), max_batch = 2: 1 image, then 3
+    (chunks of 2 and 1: the one workspace grows), then 1 again."""
+    from a_link_amd import resnet50 as R
+    size = (197, 197)
+    params = R.synthetic_params(1)
+    x = torch.from_numpy(_pixels(3, size, seed=6)).cuda()
+    net = R.VGGResNet50(image_size=size, weights=params, dtype="bf16", max_batch=2)
+    _grow_shrink_case(net, R.VGGResNet50(image_size=size, weights=params, dtype="bf16", max_batch=2), x, (1, 3, 1))

@@ -366,7 +366,7 @@ def _r50_gpu(gpu, dtype, size, x, dfeat, preprocessed, want_cache=True):
     feat = net.embed_with_cache(xd, preprocessed=preprocessed)
     assert torch.equal(feat, net.embed_device(xd, preprocessed=preprocessed)), "the cached forward is not the plain forward bit for bit"
     g = net.input_gradient(dfd)
-    cache = _cache(gpu.load(), "alink_debug_resnet50_grad_cache_info", net.h, n, net._grad_ws[0], TORCH_DT[dtype]) if want_cache else None
+    cache = _cache(gpu.load(), "alink_debug_resnet50_grad_cache_info", net.h, n, net.ws.tensor("grad"), TORCH_DT[dtype]) if want_cache else None
     return feat.cpu(), g.cpu().numpy(), cache
 
 
@@ -481,7 +481,7 @@ def _ir_gpu(gpu, params, dtype, x, demb, nchw, want_cache=True):
     g = bb.input_gradient(torch.from_numpy(demb).cuda())
     if nchw:
         g = g.permute(0, 2, 3, 1)
-    cache = _cache(gpu.load(), "alink_debug_backbone_grad_cache_info", bb.h, n, bb._ws["grad"][0], TORCH_DT[dtype]) if want_cache else None
+    cache = _cache(gpu.load(), "alink_debug_backbone_grad_cache_info", bb.h, n, bb.ws.tensor("grad"), TORCH_DT[dtype]) if want_cache else None
     return emb.double().cpu().numpy(), g.contiguous().cpu().numpy(), cache
 
 

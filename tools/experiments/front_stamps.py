@@ -10,8 +10,7 @@ from a_link_amd.backbone import IRBackbone
 lib = _abi.load()
 lib.alink_debug_set_stamps.argtypes = [C.c_void_p]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 292
-bb = IRBackbone(W.synthetic_ir_params((1, 1, 1, 1), seed=1), dtype="bf16", max_batch=n)
-bb._set_shards(1) if hasattr(bb, "_set_shards") else None
+bb = IRBackbone(W.synthetic_ir_params((1, 1, 1, 1), seed=1), dtype="bf16", max_batch=n, shards_per_call=1)
 x = torch.randint(0, 256, (n, 112, 112, 3), dtype=torch.uint8).cuda()
 for _ in range(3):
     bb.profile(x)

@@ -53,8 +53,8 @@ def main(argv=None):
     out = torch.empty((n, 2048), dtype=torch.float32, device="cuda")
     dpix = torch.empty((n, 224, 224, 3), dtype=torch.float32, device="cuda")
     lib, st = net.lib, _abi.current_stream(net.device)
-    ws, wsb = net._workspace(n)
-    gws, gwsb = net._grad_workspace(n)
+    ws, wsb = net.ws.get(n)
+    gws, gwsb = net.ws.get(n, "grad")
 
     def fwd():
         _abi.check(lib.alink_resnet50_embed(net.h, _abi.ptr(x), n, 0, _abi.ptr(out), C.c_void_p(ws), wsb, st), "embed")

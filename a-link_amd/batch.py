@@ -14,7 +14,10 @@ utility against its distance to everything labelled or already picked.  With N p
 are host float64 NumPy + sklearn's pairwise_distances_argmin_min, one full call per pick, any sklearn metric.  Without
 labelled rows the first pick is the row with the least mean distance to all rows (modAL's cold start); it is masked like
 every other pick.  `ranked_batch_device` is the same rule with the Euclidean metric for a pool resident on the GPU
-(alink_ranked_batch, batch.hip: one streaming pass per pick); it has no cold start.
+(alink_ranked_batch, batch.hip: one streaming pass per pick); it needs a labelled row.  `ranked_batch_cold_device` is the
+form without one: the cold start's row comes from density.information_density_device (alink_information_density,
+density.hip: every pool row against every other, the host form's N x N float64 matrix never built) and becomes the one
+labelled row of ranked_batch_device over the rest of the pool.
 
 A pair input X = [left, right] is represented by the rows |left - right|, which is what the pair scorer itself sees
 (code/siamese.py:27-35); the learner's X_training likewise.
@@ -107,21 +110,8 @@ def _f32_matrix(name, t, torch, device=None, cols=None):
     return t.contiguous()
 
 
-def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
-    """Ranked batch selection of a pool on the GPU (alink_ranked_batch), Euclidean metric.
-
-    rows         the pool: a CUDA float32 (N, D) tensor, or a tuple (left, right, li, ri) — feature tables (., D) and int32
-                 index vectors (N,): row n is |left[li[n]] - right[ri[n]]|, formed on the fly, never materialised
-    utility      CUDA float32 (N,), larger = more informative (uncertainty.score_device, disagreement.score_members_device)
-    labeled      CUDA float32 (M, D), M >= 1: the labelled rows, materialised (pairs as |l - r|)
-    n_instances  batch size, clipped to N
-    alpha        None: modAL's schedule (N - t) / (N + M); a number in [0, 1]: a fixed weight of the distance term
-                 (0 = plain top-k order on the utility, 1 = farthest-point order)
-    -> (idx int32 (k,), scores float32 (k,)) on the device: the picks in order and the score each had when picked; ties go
-    to the lower index, a NaN utility never wins.  Nothing is synchronised or read back except, in the pair form, the
-    range check of li / ri."""
-    import torch
-    from . import _abi, net_host
+def _pool_rows(rows, torch):
+    """the pool argument of the device forms, checked -> (left, right, li, ri, N, D, device); right = li = ri = None for a row table"""
     if isinstance(rows, (tuple, list)):
         if len(rows) != 4:
             raise ValueError("rows: an (N, D) tensor or a tuple (left, right, li, ri)")
@@ -146,16 +136,39 @@ def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
         dev, D = left.device, left.shape[1]
         right = li = ri = None
         N = left.shape[0]
+    return left, right, li, ri, N, D, dev
+
+
+def _utility_vector(utility, N, dev, torch):
+    if not isinstance(utility, torch.Tensor) or not utility.is_cuda or utility.device != dev:
+        raise ValueError("utility: a CUDA tensor on the pool's device is needed")
+    if utility.dtype is not torch.float32 or utility.dim() != 1 or utility.numel() != N:
+        raise ValueError("utility: float32 of shape (%d,) is needed (got %s, shape %s)" % (N, utility.dtype, tuple(utility.shape)))
+    return utility.contiguous()
+
+
+def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
+    """Ranked batch selection of a pool on the GPU (alink_ranked_batch), Euclidean metric.
+
+    rows         the pool: a CUDA float32 (N, D) tensor, or a tuple (left, right, li, ri) — feature tables (., D) and int32
+                 index vectors (N,): row n is |left[li[n]] - right[ri[n]]|, formed on the fly, never materialised
+    utility      CUDA float32 (N,), larger = more informative (uncertainty.score_device, disagreement.score_members_device)
+    labeled      CUDA float32 (M, D), M >= 1: the labelled rows, materialised (pairs as |l - r|)
+    n_instances  batch size, clipped to N
+    alpha        None: modAL's schedule (N - t) / (N + M); a number in [0, 1]: a fixed weight of the distance term
+                 (0 = plain top-k order on the utility, 1 = farthest-point order)
+    -> (idx int32 (k,), scores float32 (k,)) on the device: the picks in order and the score each had when picked; ties go
+    to the lower index, a NaN utility never wins.  Nothing is synchronised or read back except, in the pair form, the
+    range check of li / ri."""
+    import torch
+    from . import _abi, net_host
+    left, right, li, ri, N, D, dev = _pool_rows(rows, torch)
     labeled = _f32_matrix("labeled", labeled, torch, dev, D)
     M = labeled.shape[0]
     if M == 0:
         raise ValueError("ranked_batch_device needs at least one labelled row: the cold start (the row nearest to all others) is "
                          "O(N^2 D) at pool scale and stays on the host (batch.ranked_batch)")
-    if not isinstance(utility, torch.Tensor) or not utility.is_cuda or utility.device != dev:
-        raise ValueError("utility: a CUDA tensor on the pool's device is needed")
-    if utility.dtype is not torch.float32 or utility.dim() != 1 or utility.numel() != N:
-        raise ValueError("utility: float32 of shape (%d,) is needed (got %s, shape %s)" % (N, utility.dtype, tuple(utility.shape)))
-    utility = utility.contiguous()
+    utility = _utility_vector(utility, N, dev, torch)
     if alpha is not None and not 0.0 <= float(alpha) <= 1.0:
         raise ValueError("alpha = %r: None for the schedule, or a weight in [0, 1]" % (alpha,))
     if int(n_instances) < 1:
@@ -169,4 +182,47 @@ def ranked_batch_device(rows, utility, labeled, n_instances, alpha=None):
                                       _abi.ptr(utility), int(n_instances), -1.0 if alpha is None else float(alpha), _abi.ptr(idx),
                                       _abi.ptr(scores), sp, _abi.current_stream(dev)),
                "alink_ranked_batch")
+    return idx, scores
+
+
+def ranked_batch_cold_device(rows, utility, n_instances, alpha=None):
+    """Ranked batch selection on the GPU WITHOUT labelled rows: modAL's cold start, then ranked_batch_device.
+
+    Pick 0 is the pool's central row c, the row with the least mean Euclidean distance to all rows
+    (density.information_density_device, want=("central",)); row c, materialised as (1, D), is the labelled set, and the pool
+    without it goes to ranked_batch_device for the other n_instances - 1 picks, whose indices are mapped back
+    (idx + (idx >= c)).  With a pool of N - 1 and one labelled row the schedule is alpha_t = (N - 1 - t) / N: the host
+    ranked_batch's after its cold start.  The pair form drops position c from li / ri; the row form gathers the other
+    N - 1 rows, which COPIES the table.  One scalar is read back (c: it decides what the second call is given), besides the
+    pair form's range check of li / ri.
+
+    rows, utility, n_instances, alpha as in ranked_batch_device.
+    -> (idx int32 (k,), scores float32 (k,)) on the device, k = min(n_instances, N); scores[0] is NaN: the cold pick has no
+    score."""
+    import torch
+    from . import density
+    left, right, li, ri, N, D, dev = _pool_rows(rows, torch)
+    utility = _utility_vector(utility, N, dev, torch)
+    if alpha is not None and not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha = %r: None for the schedule, or a weight in [0, 1]" % (alpha,))
+    if int(n_instances) < 1:
+        raise ValueError("n_instances = %r must be at least 1" % (n_instances,))
+    if N < 1:
+        raise ValueError("ranked_batch_cold_device: the pool is empty")
+    pool = left if li is None else (left, right, li, ri)
+    central = density.information_density_device(pool, want=("central",))["central"]
+    c = int(central)
+    if c < 0:
+        raise ValueError("ranked_batch_cold_device: no pool row has a mean distance that is a number")
+    idx, scores = central, torch.full((1,), float("nan"), dtype=torch.float32, device=dev)
+    if int(n_instances) > 1 and N > 1:
+        keep = torch.cat((torch.arange(0, c, device=dev), torch.arange(c + 1, N, device=dev)))
+        if li is None:
+            labeled, rest = left[c:c + 1], left[keep]
+        else:
+            labeled = (left[li[c].long()] - right[ri[c].long()]).abs().unsqueeze(0)
+            rest = (left, right, li[keep], ri[keep])
+        more, more_scores = ranked_batch_device(rest, utility[keep], labeled, int(n_instances) - 1, alpha=alpha)
+        more = more + (more >= c).to(torch.int32)                                # (a -1, nothing but NaN scores left, stays -1)
+        idx, scores = torch.cat((idx, more)), torch.cat((scores, more_scores))
     return idx, scores

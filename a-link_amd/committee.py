@@ -84,17 +84,42 @@ class Bagging:
         disagreement_indexed; "margin" is refused (a SMALLER margin is the more uncertain).  -> (idx int32 (k,), scores (k,))
         on the device, batch.ranked_batch_device's.  Members behind their own feature extractors (lists of matrices) have no
         single row space: score them with disagreement_indexed and call batch.ranked_batch_device on the rows of choice."""
-        from . import batch as _batch, disagreement as _dis, uncertainty as _unc
+        from . import batch as _batch
+        self._one_feature_space(emb_left, emb_right)
+        utility = self._indexed_utility(emb_left, emb_right, li, ri, kind)
+        return _batch.ranked_batch_device((emb_left, emb_right, li, ri), utility, labeled, n_instances, alpha=alpha)
+
+    @staticmethod
+    def _one_feature_space(emb_left, emb_right):
         if isinstance(emb_left, (list, tuple)) or isinstance(emb_right, (list, tuple)):
             raise ValueError("ranked_batch_indexed measures distances in one feature space: one left and one right matrix, not one per member")
+
+    def _indexed_utility(self, emb_left, emb_right, li, ri, kind):
+        from . import disagreement as _dis, uncertainty as _unc
         if kind in ("uncertainty", "entropy"):
-            utility = _unc.score_device(self.predict_indexed(emb_left, emb_right, li, ri), kind)
-        elif kind in _dis.KINDS:
-            utility = self.disagreement_indexed(emb_left, emb_right, li, ri, kind=kind)
-        else:
-            raise ValueError("unknown utility kind %r: choose among %s (margin: smaller is more uncertain, so it cannot weigh "
-                             "against a distance)" % (kind, ["uncertainty", "entropy"] + list(_dis.KINDS)))
-        return _batch.ranked_batch_device((emb_left, emb_right, li, ri), utility, labeled, n_instances, alpha=alpha)
+            return _unc.score_device(self.predict_indexed(emb_left, emb_right, li, ri), kind)
+        if kind in _dis.KINDS:
+            return self.disagreement_indexed(emb_left, emb_right, li, ri, kind=kind)
+        raise ValueError("unknown utility kind %r: choose among %s (margin: smaller is more uncertain, so it cannot weigh "
+                         "against a distance)" % (kind, ["uncertainty", "entropy"] + list(_dis.KINDS)))
+
+    def density_indexed(self, emb_left, emb_right, li, ri, reference=None):
+        """Extension: the information density (density.py; modAL.density) of the pairs (li[p], ri[p]) gathered from ONE left
+        and ONE right embedding matrix on device, each pair as the row |left - right| — its mean similarity 1 / (1 + distance)
+        to the rows `reference` (R, D), or to all the pairs when reference is None.  -> (N,) float32 on the device,
+        density.information_density_device's; weigh a utility with it through density.density_weighted."""
+        from . import density as _density
+        self._one_feature_space(emb_left, emb_right)
+        return _density.information_density_device((emb_left, emb_right, li, ri), reference=reference)["density"]
+
+    def ranked_batch_cold_indexed(self, emb_left, emb_right, li, ri, n_instances, kind="entropy", alpha=None):
+        """Extension: ranked_batch_indexed before anything is labelled — the first pick is the pair nearest to all others
+        (modAL's cold start), the rest weigh the utility against the distance to it and to the picks so far.  `kind` as in
+        ranked_batch_indexed.  -> (idx int32 (k,), scores (k,)) on the device, batch.ranked_batch_cold_device's (scores[0] is NaN)."""
+        from . import batch as _batch
+        self._one_feature_space(emb_left, emb_right)
+        utility = self._indexed_utility(emb_left, emb_right, li, ri, kind)
+        return _batch.ranked_batch_cold_device((emb_left, emb_right, li, ri), utility, n_instances, alpha=alpha)
 
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""

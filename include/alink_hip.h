@@ -606,12 +606,48 @@ int alink_topk(const float* dev_scores, int64_t P, int k, int largest, int32_t* 
  * fl(fl(alpha fl(1 - s)) + fl(fl(1 - alpha) u)) with s = fl(1 / fl(1 + fl(sqrt(d2)))), no product contracted into the sum.
  * The call enqueues 1 + k + 1 launches on `stream` and returns: no host synchronisation, nothing read back.
  * Limits (ALINK_EINVAL beyond): 1 <= N < 2^31, 1 <= D <= 8192 (the picked row is held in LDS), M >= 1 (the cold start — the
- * row nearest to all others — is O(N^2 D) and stays on the host: a-link_amd/batch.py), k >= 1, alpha <= 1 (alpha < 0: the
- * schedule).  dev_scratch >= alink_ranked_batch_scratch_bytes(N, k), 256-byte aligned. */
+ * row nearest to all others — is alink_information_density's central row, made the one labelled row of this call by
+ * batch.ranked_batch_cold_device: a-link_amd/batch.py), k >= 1, alpha <= 1 (alpha < 0: the schedule).
+ * dev_scratch >= alink_ranked_batch_scratch_bytes(N, k), 256-byte aligned. */
 size_t alink_ranked_batch_scratch_bytes(int64_t N, int k);
 int alink_ranked_batch(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
                        const float* dev_labeled, int64_t M, const float* dev_utility, int k, float alpha, int32_t* dev_idx,
                        float* dev_scores, void* dev_scratch, void* stream);
+/* Information density (modAL.density: Settles & Craven 2008) and the cold start of the ranked batch (modAL.batch's
+ * select_cold_start_instance), Euclidean metric: EXTENSION, no reference driver calls it.  N pool rows x_n of D floats against
+ * R reference rows z_j: dev_ref, a materialised (R, D) table, or — dev_ref == NULL, R == N — the pool itself; self-pairs
+ * count, as in modAL (d = 0, s = 1).
+ *   d_nj = sqrt(|x_n - z_j|^2),  s_nj = 1 / (1 + d_nj)
+ *   dev_density[n]       = (sum_j s_nj) / R                 modAL's information_density when the pool is its own reference
+ *   dev_mean_distance[n] = (sum_j d_nj) / R
+ *   dev_central[0]       = argmin_n sum_j d_nj              the cold start's row; `<` comparisons, ties to the lower index, a
+ *                                                           NaN sum never wins, -1 when nothing but NaN sums is left
+ * Any of the three outputs may be NULL, not all.  The pool has the two row forms of alink_ranked_batch (dev_li == NULL: dev_x is
+ * the (N, D) row table; otherwise row n is |dev_x[dev_li[n]] - dev_r[dev_ri[n]]|, formed on the fly, never materialised, the
+ * indices NOT range-checked).
+ * Arithmetic is pinned: |x_n - z_j|^2 is alink_ranked_batch's — float32, direct differences, one fused multiply-add per element
+ * in the one order that depends on D alone (element e to lane (e / 4) % 64, ascending per lane, then an xor butterfly over the
+ * 64 lanes; rows zero-padded), never |a|^2 + |b|^2 - 2ab — the same bits in both row forms; d = fl(sqrt(d2)) and
+ * s = fl(1 / fl(1 + d)) in float32, both correctly rounded; a row's two sums are FLOAT64, sum_j (double)s and sum_j (double)d:
+ * distances concentrate in high dimension, rows' densities then differ in their low digits, and a float32 sum of 200,000 terms
+ * would throw those away.  The outputs are the float32 of the float64 quotient by (double)R; the argmin compares the float64 sums.
+ * Summation order, a function of (R, D) alone — no atomics, so results are bit-reproducible from run to run: the reference rows
+ * pass in tiles of T = 8192 / Dp rows in ascending order (Dp = D rounded up to a multiple of 4; T rounded down to a multiple
+ * of 16 when above 16); a pool row has 16 partial sums, and the reference row at position p of its tile goes to partial c with
+ * 4 (c & 3) + (c >> 2) == p % 16; a partial adds its terms in ascending reference order; after the last tile the 16 partials
+ * meet in an xor butterfly (8, 4, 2, 1).
+ * The call enqueues one launch, two when dev_central is given, on `stream` and returns: no host synchronisation, nothing read
+ * back.  Limits (ALINK_EINVAL beyond, nothing launched): 1 <= N < 2^31, 1 <= R < 2^31 (R == N without dev_ref), 1 <= D <= 8192
+ * (a reference row is held in LDS), at least one output.  dev_scratch is needed for dev_central only:
+ * >= alink_information_density_scratch_bytes(N), 256-byte aligned.  Not here: other metrics (a-link_amd/density.py has them on
+ * the host), several ranks' pools in one call. */
+size_t alink_information_density_scratch_bytes(int64_t N);
+int alink_information_density(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                              const float* dev_ref, int64_t R,  /* NULL: the pool is its own reference, R == N */
+                              float* dev_density,               /* (N) or NULL */
+                              float* dev_mean_distance,         /* (N) or NULL */
+                              int32_t* dev_central,             /* (1) or NULL */
+                              void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

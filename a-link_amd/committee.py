@@ -76,12 +76,31 @@ class Bagging:
         probs = _head.committee_member_probs_device(hs, emb_left, emb_right, li, ri)
         return _dis.score_members_device(probs, want=(kind,))[kind]
 
+    def egl_indexed(self, emb_left, emb_right, li, ri):
+        """Extension: the committee's expected gradient length (egl.py) of the pairs (li[p], ri[p]) gathered from embedding
+        matrices on device — the mean over the members of each member's OWN EGL (a member's gradient is its own), summed in
+        member order on the device, one divide.  emb_left / emb_right may be lists with one matrix per member, as in
+        predict_indexed.  -> (P,) float32 on the device."""
+        from . import egl as _egl
+        hs = self._device_heads()
+        if hs is None:
+            raise TypeError("egl_indexed needs DenseHead members")
+        per_member = isinstance(emb_left, (list, tuple))
+        if per_member and (len(emb_left) != len(hs) or not isinstance(emb_right, (list, tuple)) or len(emb_right) != len(hs)):
+            raise ValueError("%d members but %d / %d feature matrices" % (len(hs), len(emb_left), len(emb_right) if isinstance(emb_right, (list, tuple)) else 1))
+        out = None
+        for m, h in enumerate(hs):
+            L, R = (emb_left[m], emb_right[m]) if per_member else (emb_left, emb_right)
+            out = _egl.expected_gradient_length_device(h, L, R, li, ri, egl_out=out, accumulate=m > 0,
+                                                       final_div=float(len(hs)) if m == len(hs) - 1 else 0.0)["egl"]
+        return out
+
     def ranked_batch_indexed(self, emb_left, emb_right, li, ri, labeled, n_instances, kind="entropy", alpha=None):
         """Extension: a ranked batch (batch.py; modAL.batch) of n_instances among the pairs (li[p], ri[p]) gathered from ONE
         left and ONE right embedding matrix on device — the utility weighed against each pair's distance, as the row
         |left - right|, to the labelled rows `labeled` (M, D) and to the picks so far, so near-duplicate pairs do not fill
-        the batch.  `kind`: "uncertainty" / "entropy" of predict_indexed's mean (uncertainty.score_device), or a kind of
-        disagreement_indexed; "margin" is refused (a SMALLER margin is the more uncertain).  -> (idx int32 (k,), scores (k,))
+        the batch.  `kind`: "uncertainty" / "entropy" of predict_indexed's mean (uncertainty.score_device), a kind of
+        disagreement_indexed, or "egl" (egl_indexed); "margin" is refused (a SMALLER margin is the more uncertain).  -> (idx int32 (k,), scores (k,))
         on the device, batch.ranked_batch_device's.  Members behind their own feature extractors (lists of matrices) have no
         single row space: score them with disagreement_indexed and call batch.ranked_batch_device on the rows of choice."""
         from . import batch as _batch
@@ -100,8 +119,10 @@ class Bagging:
             return _unc.score_device(self.predict_indexed(emb_left, emb_right, li, ri), kind)
         if kind in _dis.KINDS:
             return self.disagreement_indexed(emb_left, emb_right, li, ri, kind=kind)
+        if kind == "egl":
+            return self.egl_indexed(emb_left, emb_right, li, ri)
         raise ValueError("unknown utility kind %r: choose among %s (margin: smaller is more uncertain, so it cannot weigh "
-                         "against a distance)" % (kind, ["uncertainty", "entropy"] + list(_dis.KINDS)))
+                         "against a distance)" % (kind, ["uncertainty", "entropy"] + list(_dis.KINDS) + ["egl"]))
 
     def density_indexed(self, emb_left, emb_right, li, ri, reference=None):
         """Extension: the information density (density.py; modAL.density) of the pairs (li[p], ri[p]) gathered from ONE left

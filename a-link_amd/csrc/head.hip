@@ -19,63 +19,12 @@
 //   over the 2 outputs; sample-weighted batch loss = mean(w*l) / mean(w != 0); 'accuracy' resolves
 //   to binary_accuracy = mean(round(p) == y) (round half to even), not weighted;
 //   Adadelta: a = rho*a + (1-rho)*g^2; u = g*sqrt(d+eps)/sqrt(a+eps); p -= lr*u; d = rho*d+(1-rho)*u^2.
-#include "alink_common.h"
-#include "net_host.h"
+#include "head_handle.h"
 
 #include <algorithm>
 #include <vector>
 
 using namespace alink;
-
-struct alink_head {
-    int device = -1;             // the device the handle's memory lives on (current at create)
-    int D, h1, h2;
-    int od = 2;                  // outputs: 2 = Dense(2)+softmax (code/siamese.py:31-32), 1 = Dense(1, sigmoid) (code/siamese3.py:25)
-    float lr, rho, eps;
-    size_t nparams;
-    size_t oW1, ob1, oW2, ob2, oW3, ob3;
-    float* d_params = nullptr;   // Keras layout: kernel (in,out) row-major, bias; per layer
-    float* d_grads = nullptr;
-    float* d_acc = nullptr;      // Adadelta accumulators
-    float* d_dacc = nullptr;     // Adadelta delta accumulators
-    float* d_w1p = nullptr;      // W1 packed for the MFMA forward: [D/8][h1][2][4]
-    float* d_w2p = nullptr;      // W2 packed: [h1/8][h2][2][4]
-    bool packed_dirty = true;
-    // bf16 compute mode (alink_head_set_compute_dtype; BASELINE configs[4] "bf16 fine-tune", mixed precision):
-    // master parameters, gradients and Adadelta state stay f32; the forward / backward GEMM operands are bf16 —
-    // weights from d_pq (2-byte copy of the flat parameter vector, kept current by the update kernels of the
-    // batch<=32 step, else re-quantised lazily), activations and activation gradients rounded to bf16 where they are
-    // produced; products are exact in f32 and accumulate in f32.  d_pqf holds the same bf16 values widened to f32 for
-    // the large-batch chain and the MFMA predict kernel (a derived cache like d_w1p / d_w2p).  Biases are not quantised.
-    int qmode = 0;
-    __bf16* d_pq = nullptr;
-    float* d_pqf = nullptr;
-    __bf16* d_wt = nullptr;      // bf16 mode, predict on the bf16 matrix cores: W1^T [h1][D] then W2^T [h2][h1] (re-derived with the packed copies)
-    bool pq_dirty = true, pqf_dirty = true;
-    // train/eval scratch for up to `cap` rows
-    int cap = 4096;
-    float *d_dm = nullptr, *d_z1 = nullptr, *d_z2 = nullptr, *d_dz1 = nullptr, *d_dz2 = nullptr,
-          *d_dz3 = nullptr, *d_p = nullptr;
-    float* d_tiny = nullptr;     // per-row-group partials of the tiny-batch train step
-    float* d_mini = nullptr;     // Dense1 partial sums of SmallRes' three-launch step ([D / 32][n][128]); only for that head shape
-    unsigned* d_counter = nullptr;   // row groups finished (tiny_eval), 0 between launches
-    DeviceAllocs mem;
-    // hipGraph cache of the fine-tune step (a launch-bound chain of 8-9 small kernels): one executable
-    // graph per distinct (operand pointers, n, grad_scale, apply); replayed while the caller keeps
-    // feeding the same buffers (DenseHead stages every batch into persistent tensors for that purpose)
-    struct StepGraph {
-        const void *L, *R, *y, *sw, *metrics;
-        int n, apply;
-        float grad_scale, lr;
-        hipGraphExec_t exec;
-    };
-    std::vector<StepGraph> graphs;
-    bool use_graph = false;     // measured on MI355X: replay 67.8 us vs 66.2 us of plain launches — the chain is
-                                // bound by kernel-to-kernel dependency latency, not by launch cost; kept as an option
-    ~alink_head() {
-        for (auto& g : graphs) (void)hipGraphExecDestroy(g.exec);
-    }
-};
 
 namespace {
 
@@ -105,10 +54,6 @@ __global__ void quantize_kernel(const float* __restrict__ prm, __bf16* __restric
     pqf[i] = (float)b;
 }
 
-constexpr int TP = 32;          // pairs per workgroup in the MFMA forward
-constexpr int ROWP = TP * 8 + 4;  // floats per k8 block in LDS (pad 4: conflict-free b128 writes)
-constexpr int KC = 512;         // K chunk staged per pass
-
 struct HeadFwd {
     const float *L, *R;
     const int32_t *li, *ri;
@@ -130,6 +75,15 @@ __global__ void pack_kernel(const float* __restrict__ w, float* __restrict__ wp,
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)in * out) return;
     const int k = (int)(i / out), c = (int)(i - (long long)k * out);
+    const int k8 = k >> 3, kk = k & 7, h = kk & 1, s = kk >> 1;
+    wp[((size_t)k8 * out + c) * 8 + h * 4 + s] = w[i];
+}
+
+// the same layout for W^T: W (out,in) row-major -> [in/8][out][2][4]
+__global__ void pack_transposed_kernel(const float* __restrict__ w, float* __restrict__ wp, int in, int out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)in * out) return;
+    const int c = (int)(i / in), k = (int)(i - (long long)c * in);
     const int k8 = k >> 3, kk = k & 7, h = kk & 1, s = kk >> 1;
     wp[((size_t)k8 * out + c) * 8 + h * 4 + s] = w[i];
 }
@@ -852,6 +806,8 @@ int ensure_packed(alink_head* h, hipStream_t st) {
                        h->d_w1p, h->D, h->h1);
     hipLaunchKernelGGL(pack_kernel, g1((long long)h->h1 * h->h2), dim3(256), 0, st, src + h->oW2,
                        h->d_w2p, h->h1, h->h2);
+    if (h->d_w2tp)
+        hipLaunchKernelGGL(pack_transposed_kernel, g1((long long)h->h1 * h->h2), dim3(256), 0, st, src + h->oW2, h->d_w2tp, h->h2, h->h1);
     if (h->qmode && h->d_wt) {      // W1^T, W2^T in bf16 for head_fwd_bf16_kernel
         hipLaunchKernelGGL(transpose_bf16_kernel, g1((long long)h->D * h->h1), dim3(256), 0, st, h->d_pq + h->oW1, h->d_wt,
                            h->D, h->h1);
@@ -864,13 +820,6 @@ int ensure_packed(alink_head* h, hipStream_t st) {
 }
 
 bool g_use_bf16_mfma = true;       // A/B: bf16 mode's predict on the bf16 matrix cores (else the f32-input kernel with rounding)
-
-size_t fwd_lds_bytes(int h1) {
-    const size_t a = (size_t)(KC / 8) * ROWP, b = (size_t)(h1 / 8) * ROWP, c = 4 * TP * 64 + TP * 64;
-    size_t m = a > b ? a : b;
-    if (c > m) m = c;
-    return m * sizeof(float);
-}
 
 int launch_fwd(alink_head* h, const float* L, const float* R, const int32_t* li, const int32_t* ri,
                long long P, float* probs, int accumulate, float final_div, hipStream_t st, int matN = 0,
@@ -1972,6 +1921,8 @@ int head_init_attrs() {
 }
 
 }  // namespace
+
+int alink::head_ensure_packed(alink_head* h, hipStream_t st) { return ensure_packed(h, st); }
 
 extern "C" {
 

@@ -324,6 +324,12 @@ class DenseHead(KerasFitMixin, Handle):
                                                _abi.ptr(out), _abi.current_stream(self.device)), "alink_head_forward")
         return out
 
+    def expected_gradient_length_device(self, L, R, li=None, ri=None, want=("egl",)):
+        """EXTENSION (egl.py): expected gradient length, probabilities and gradient embeddings of the pairs
+        (L[n], R[n]) or (L[li[n]], R[ri[n]]) on the device -> {name: CUDA tensor}; egl.expected_gradient_length_device's."""
+        from . import egl as _egl
+        return _egl.expected_gradient_length_device(self, L, R, li, ri, want=want)
+
     def predict(self, X, batch_size=1024, verbose=0):
         """Keras Model.predict([L, R]) (reference code/siamese.py:131).  batch_size is accepted for
         API compatibility; the kernel tiles the pairs itself."""

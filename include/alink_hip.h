@@ -648,6 +648,31 @@ int alink_information_density(const float* dev_x, const float* dev_r, const int3
                               float* dev_mean_distance,         /* (N) or NULL */
                               int32_t* dev_central,             /* (1) or NULL */
                               void* dev_scratch, void* stream);
+/* Expected gradient length (Settles, Craven & Ray 2008) and the last layer's gradient embedding (BADGE: Ash et al. 2020) of P
+ * pairs through one head: EXTENSION, no reference driver calls it.  The pairs are alink_head_forward's (dev_li / dev_ri index
+ * the two feature tables, NULL = identity; the indices are NOT range-checked).  For pair x let l_c(x) be the loss
+ * alink_head_train_step computes on the batch {x} with target class c and sample weight 1, g_c(x) its gradient over all six
+ * parameter tensors:
+ *   dev_egl[p]   = sum over c in {0, 1} of P(c | x) |g_c(x)|_2      P(c | x) = the head's probability (out_dim 1: p and 1 - p)
+ *   dev_probs[p] = alink_head_forward's probabilities, bit for bit
+ *   dev_emb[p][c * h2 + j] = (p_c - [c == yhat]) a2[j]               yhat = argmax p, ties to class 0 (out_dim 1: p > 0.5);
+ *                                                                    the last layer's weight gradient for the label yhat
+ * No per-sample weight gradient is formed: with d = |l - r|, a1 = relu(z1), a2 = relu(z2),
+ *   u = (W3[:,0] - W3[:,1]) . [z2 > 0], n3 = 2   (out_dim 1: u = W3[:,0] . [z2 > 0], n3 = 1),   v = (u W2^T) . [z1 > 0],
+ *   G^2 = n3 (|a2|^2 + 1) + |u|^2 (|a1|^2 + 1) + |v|^2 (|d|^2 + 1),    egl = 2 p0 p1 sqrt(G^2)   (out_dim 1: 2 p (1 - p) sqrt(G^2)).
+ * A row with an output outside [1e-7, 1 - 1e-7] has egl exactly 0 and a zero embedding: the loss clips there and the train
+ * step's gradient is zero.  float32 throughout, one launch, every sum in an order fixed by the head's shape (no atomics): a
+ * pair's outputs do not depend on P or on where the pair stands.
+ * accumulate / final_div act on dev_egl only, as the committee mean's do on probabilities: accumulate adds to the value already
+ * there, final_div > 0 divides the sum by it (one call per member, the last with final_div = the number of members).
+ * P == 0 writes nothing.  ALINK_EINVAL, nothing launched: a NULL head or table, all three outputs NULL, P < 0 or above
+ * 2^29 - 32, accumulate without dev_egl, a head in the bf16 compute mode (this is the exact form). */
+int alink_head_egl(alink_head_t* h, const float* dev_L, const float* dev_R, const int32_t* dev_li, const int32_t* dev_ri, int64_t P,
+                   int accumulate, float final_div,       /* committee mean, on dev_egl */
+                   float* dev_egl,                         /* [P]            or NULL */
+                   float* dev_probs,                       /* [P][od]        or NULL */
+                   float* dev_emb,                         /* [P][od*h2]     or NULL */
+                   void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

@@ -187,6 +187,8 @@ PROTOTYPES = {
     "alink_ranked_batch": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "alink_information_density_scratch_bytes": (_sz, [_i64]),
     "alink_information_density": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "alink_kmeanspp_scratch_bytes": (_sz, [_i64, _i]),
+    "alink_kmeanspp": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -95,6 +95,29 @@ class Bagging:
                                                        final_div=float(len(hs)) if m == len(hs) - 1 else 0.0)["egl"]
         return out
 
+    def badge_indexed(self, emb_left, emb_right, li, ri, n_instances, uniforms=None, seed=None):
+        """Extension: a BADGE batch (badge.py) of the pairs (li[p], ri[p]) gathered from embedding matrices on device.  The
+        committee's gradient embedding of a pair is its members' embeddings side by side (a member's gradient is its own):
+        D = members x out_dim x h2 columns, at most the 8,192 a picked row may have; k-means++ seeding over those rows.
+        emb_left / emb_right may be lists with one matrix per member, as in egl_indexed.
+        -> (idx int32 (k,), potential float64 (k,)) on the device, badge.kmeans_pp_device's."""
+        from . import badge as _badge, egl as _egl
+        hs = self._device_heads()
+        if hs is None:
+            raise TypeError("badge_indexed needs DenseHead members")
+        per_member = isinstance(emb_left, (list, tuple))
+        if per_member and (len(emb_left) != len(hs) or not isinstance(emb_right, (list, tuple)) or len(emb_right) != len(hs)):
+            raise ValueError("%d members but %d / %d feature matrices" % (len(hs), len(emb_left), len(emb_right) if isinstance(emb_right, (list, tuple)) else 1))
+        D = sum(h.out_dim * h.h2 for h in hs)
+        if D > _badge.MAX_D:
+            raise ValueError("the committee's gradient embedding has D = %d columns (%d members), beyond the %d a picked row may have" % (D, len(hs), _badge.MAX_D))
+        torch = hs[0].torch
+        embs = []
+        for m, h in enumerate(hs):
+            L, R = (emb_left[m], emb_right[m]) if per_member else (emb_left, emb_right)
+            embs.append(_egl.expected_gradient_length_device(h, L, R, li, ri, want=("emb",))["emb"])
+        return _badge.kmeans_pp_device(torch.cat(embs, dim=1), n_instances, uniforms=uniforms, seed=seed)
+
     def ranked_batch_indexed(self, emb_left, emb_right, li, ri, labeled, n_instances, kind="entropy", alpha=None):
         """Extension: a ranked batch (batch.py; modAL.batch) of n_instances among the pairs (li[p], ri[p]) gathered from ONE
         left and ONE right embedding matrix on device — the utility weighed against each pair's distance, as the row

@@ -26,8 +26,8 @@ the scorer itself would give, yhat = argmax p (ties to class 0; one output: p > 
 
 `expected_gradient_length`, `gradient_embedding` are host float64 NumPy; `egl_sampling` is modAL-shaped;
 `expected_gradient_length_device` is the form for a pool resident on the GPU (alink_head_egl, egl.hip: one forward pass plus
-one h2 -> h1 back-projection per pair, in one launch).  Not on the device: a bf16-mode form, BADGE's k-means++ sampling (the
-embeddings and batch.ranked_batch_device are the pieces it would need), several ranks' pools in one call.
+one h2 -> h1 back-projection per pair, in one launch).  BADGE's k-means++ sampling over the embeddings is badge.py (X10).  Not
+on the device: a bf16-mode form, several ranks' pools in one call.
 """
 import numpy as np
 

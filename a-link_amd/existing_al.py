@@ -9,13 +9,19 @@ from .learners import ActiveLearner
 
 
 def get_strategy_object(query_strategy):
-    """code/existing_al.py:43-49"""
+    """code/existing_al.py:43-49; 'egl_sampling' and 'badge_sampling' are this package's additions"""
     if query_strategy == 'uncertainty_sampling':
         return uncertainty.uncertainty_sampling
     elif query_strategy == 'margin_sampling':
         return uncertainty.margin_sampling
     elif query_strategy == 'entropy_sampling':
         return uncertainty.entropy_sampling
+    elif query_strategy == 'egl_sampling':                # EXTENSION (egl.py; DESIGN.md §0, X9)
+        from . import egl
+        return egl.egl_sampling
+    elif query_strategy == 'badge_sampling':              # EXTENSION (badge.py; DESIGN.md §0, X10)
+        from . import badge
+        return badge.badge_sampling
 
 
 def run_baseline(model, dataGen, query_strategy='uncertainty_sampling', active_ratio=1.0, out_model=None, verbose=1,

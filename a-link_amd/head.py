@@ -330,6 +330,12 @@ class DenseHead(KerasFitMixin, Handle):
         from . import egl as _egl
         return _egl.expected_gradient_length_device(self, L, R, li, ri, want=want)
 
+    def badge_device(self, L, R, li=None, ri=None, n_instances=1, uniforms=None, seed=None):
+        """EXTENSION (badge.py): a BADGE batch — k-means++ seeding over the gradient embeddings of the pairs
+        (L[n], R[n]) or (L[li[n]], R[ri[n]]) on the device -> (idx int32 (k,), potential float64 (k,)); badge.badge_device's."""
+        from . import badge as _badge
+        return _badge.badge_device(self, L, R, li, ri, n_instances=n_instances, uniforms=uniforms, seed=seed)
+
     def predict(self, X, batch_size=1024, verbose=0):
         """Keras Model.predict([L, R]) (reference code/siamese.py:131).  batch_size is accepted for
         API compatibility; the kernel tiles the pairs itself."""

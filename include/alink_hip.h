@@ -673,6 +673,44 @@ int alink_head_egl(alink_head_t* h, const float* dev_L, const float* dev_R, cons
                    float* dev_probs,                       /* [P][od]        or NULL */
                    float* dev_emb,                         /* [P][od*h2]     or NULL */
                    void* stream);
+/* k-means++ seeding (Arthur & Vassilvitskii 2007) over N pool rows of D floats: the batch rule of BADGE (Ash et al. 2020) when
+ * the rows are alink_head_egl's gradient embeddings.  EXTENSION, no reference driver calls it.  The pool has the two row forms of
+ * alink_ranked_batch (dev_li == NULL: dev_x is the (N, D) row table; otherwise row n is |dev_x[dev_li[n]] - dev_r[dev_ri[n]]|,
+ * formed on the fly, never materialised, the indices NOT range-checked).  k picks (clipped to N); dev_uniform: k float64 values
+ * in [0, 1), entry 0 never read (so the stream does not depend on `first`); first: a row index, or -1 for the row of largest
+ * squared norm.  This is the library's only SAMPLING rule, so every step of the draw is pinned:
+ *   pick 0      first, or with first = -1 the argmax_n of |x_n|^2 — float32, the squared distance to the zero row in the order
+ *               below; `>` comparisons, ties to the lower index, a NaN never enters; dev_idx[0] = -1 when no row has a norm that
+ *               is a number (every later pick is then -1 with potential 0).  dev_potential[0] = NaN.
+ *   distances   after pick p: d2_n = min(d2_n, |x_n - x_p|^2) (after pick 0: assigned) — float32, alink_ranked_batch's
+ *               arithmetic: direct differences, one fused multiply-add per element, element e to lane (e / 4) % 64, ascending per
+ *               lane, then an xor butterfly over the 64 lanes (rows zero-padded); the same bits in both row forms.  A picked row
+ *               and every exact duplicate of it has d2 = 0 exactly.
+ *   weights     w_n = (double)d2_n if 0 < d2_n < inf, else 0 (a NaN row weighs nothing).
+ *   sums        C_n = sum over m <= n of w_m, T = C_(N-1), float64;  target = uniform[t] * T, one float64 product.
+ *   pick t      the smallest n with w_n > 0 and C_n > target; if there is none (the product rounded up to T) the last row with
+ *               w > 0.  dev_potential[t] = T, the k-means potential before the pick.
+ *   exhaustion  T == 0 (fewer distinct rows than picks): pick t and every later pick are -1, their potential 0.
+ * Every comparison is of a cumulative sum against the target, never of a partial sum against target - prefix (that subtraction
+ * rounds).  The order of the float64 sums is a function of N alone — no atomics, so results are bit-identical from run to run:
+ * rows are cut into contiguous chunks of c = 8 ceil(N / 16384) rows; a chunk's sum adds, for each of 4 interleaved row-pair
+ * streams (rows 8 i + 2 v, 8 i + 2 v + 1 of the chunk in stream v), its weights in ascending order, then ((s0 + s1) + s2) + s3;
+ * the chunk sums are accumulated in ascending chunk order (blocks of 8 chunks: the blocks' totals meet in a Hillis-Steele scan
+ * over 64 blocks and an ascending sum over the 4 groups of 64, then each block adds its chunks one after another from the sum
+ * of everything below it); inside the chosen chunk C_n = (that chunk's base + the totals of the 64-row segments before n's, one
+ * after another) + a Hillis-Steele scan inside n's segment.  Where every w is an integer and T < 2^53 no sum rounds, and the
+ * picks are those of np.cumsum / np.searchsorted(side="right") (a-link_amd/badge.py: kmeans_pp).
+ * The call enqueues (first == -1 ? 1 : 0) + (k - 1) + 1 launches on `stream` and returns: no host synchronisation, nothing read
+ * back.  ALINK_EINVAL, nothing launched and no output touched: a NULL argument, a pair form without dev_r / dev_ri, N outside
+ * 1 .. 2^31 - 1, D outside 1 .. 8192 (the picked row is held in LDS), k < 1, first outside -1 .. N - 1, dev_scratch not 256-byte
+ * aligned.  dev_scratch >= alink_kmeanspp_scratch_bytes(N, k).  Not here: several ranks' pools in one call, labelled rows as
+ * centres that exist before the first pick, fusing the embedding into the distance pass. */
+size_t alink_kmeanspp_scratch_bytes(int64_t N, int k);
+int alink_kmeanspp(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                   const double* dev_uniform, int64_t first, int k,
+                   int32_t* dev_idx,                       /* (k) picks in order, -1 = none */
+                   double* dev_potential,                  /* (k) T before each pick; [0] = NaN */
+                   void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

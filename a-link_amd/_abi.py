@@ -189,6 +189,8 @@ PROTOTYPES = {
     "alink_information_density": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "alink_kmeanspp_scratch_bytes": (_sz, [_i64, _i]),
     "alink_kmeanspp": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "alink_kmeans_scratch_bytes": (_sz, [_i64, _i, _i]),
+    "alink_kmeans": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i] + [_vp] * 7 + [_vp, _vp]),
 }
 
 _lib = None

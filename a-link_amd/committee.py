@@ -165,6 +165,26 @@ class Bagging:
         utility = self._indexed_utility(emb_left, emb_right, li, ri, kind)
         return _batch.ranked_batch_cold_device((emb_left, emb_right, li, ri), utility, n_instances, alpha=alpha)
 
+    def kmeans_sampling_indexed(self, emb_left, emb_right, li, ri, n_instances, iters=10, uniforms=None, seed=None):
+        """Extension: k-means sampling (cluster.py) of n_instances among the pairs (li[p], ri[p]) gathered from ONE left and ONE
+        right embedding matrix on device, each pair as the row |left - right|: the pairs are clustered from k-means++ seeds and
+        the pair nearest to each centre is queried.  -> (idx int32 (k,), info) on the device, cluster.kmeans_sampling_device's."""
+        from . import cluster as _cluster
+        self._one_feature_space(emb_left, emb_right)
+        return _cluster.kmeans_sampling_device((emb_left, emb_right, li, ri), n_instances, iters=iters, uniforms=uniforms, seed=seed)
+
+    def diverse_minibatch_indexed(self, emb_left, emb_right, li, ri, n_instances, kind="entropy", beta=10, iters=10, uniforms=None,
+                                  seed=None):
+        """Extension: a diverse mini-batch (cluster.py; Zhdanov 2019) of n_instances among the pairs (li[p], ri[p]) gathered from
+        ONE left and ONE right embedding matrix on device: the beta * k pairs of largest utility, clustered as rows |left - right|
+        with the utility as weight, the pair nearest to each centre queried.  `kind` as in ranked_batch_indexed.
+        -> (idx int32 (k,), info) on the device, cluster.diverse_minibatch_device's."""
+        from . import cluster as _cluster
+        self._one_feature_space(emb_left, emb_right)
+        utility = self._indexed_utility(emb_left, emb_right, li, ri, kind)
+        return _cluster.diverse_minibatch_device((emb_left, emb_right, li, ri), utility, n_instances, beta=beta, iters=iters,
+                                                 uniforms=uniforms, seed=seed)
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

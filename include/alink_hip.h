@@ -711,6 +711,47 @@ int alink_kmeanspp(const float* dev_x, const float* dev_r, const int32_t* dev_li
                    int32_t* dev_idx,                       /* (k) picks in order, -1 = none */
                    double* dev_potential,                  /* (k) T before each pick; [0] = NaN */
                    void* dev_scratch, void* stream);
+/* EXTENSION — Lloyd's k-means of a pool on the device: T iterations from given centres, the engine of k-means
+ * sampling and of the diverse mini-batch (a-link_amd/cluster.py).  The pool as alink_kmeanspp takes it: an (N, D) row table dev_x
+ * (dev_li == NULL), or row n = |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the fly.  dev_weight: (N) float32 or NULL (every
+ * weight 1); a weight that is not finite and > 0 counts as 0.  dev_centres: (K, D) float32, in: C_0, out: C_T.  The rule:
+ *   assignment  against centres C:  dot(n, j) = x_n . c_j — float32, ONE fused multiply-add per element from 0 in ascending
+ *               element order e = 0 .. D - 1 (what one MFMA accumulator gives: the order is a function of D alone, not of N, K, the
+ *               tile a row or centre falls in, 16-byte or 4-byte loads, or the row form);  cn_j = |c_j|^2 — float32, the squared
+ *               distance of c_j to the zero row in alink_ranked_batch's order (element e to lane (e / 4) % 64, one fused
+ *               multiply-add each, ascending per lane, an xor butterfly over the 64 lanes);  score(n, j) = fmaf(-2, dot(n, j), cn_j),
+ *               one rounding.  a_n = the j of least score by `<` from +inf: ties go to the lower j; a score that is NaN or +inf never
+ *               wins, so a centre with a non-finite element never takes a row and is left as it is, and a row no centre wins (a NaN
+ *               row) has a_n = -1 and d2_n = NaN and is left out of every sum and count.
+ *   distance    d2_n = |x_n - c_(a_n)|^2 for the assigned centre only — float32, direct differences in alink_ranked_batch's order
+ *               above: never negative, and comparable with the other strategies' distances.
+ *   update      c_j <- (float)(sum over a_n = j of w_n x_n / sum over a_n = j of w_n): both sums float64 (a product w_n x_n is exact
+ *               in float64), one float64 division, one rounding.  Rows of weight 0 are left out; a cluster whose weight sum is 0
+ *               keeps its centre.  Order: rows are cut into S slices of L = 256 ceil(ceil(N / S') / 256) rows, S' = 1 for
+ *               K >= 2048, else min(64, ceil(4096 / K)), S = ceil(N / L); a slice adds its rows of cluster j in ascending row order,
+ *               the slices' sums are added in ascending order from 0.
+ *   schedule    for t = 0 .. iters - 1: assign against C_t, update to C_(t+1); then one last assignment against C_iters.
+ * Outputs, any but dev_assign NULL: dev_assign (N) int32 and dev_d2 (N) float32 of the last assignment; dev_inertia (iters + 1)
+ * float64, the sum of w_n d2_n over the rows with a_n >= 0 and w_n > 0 of each assignment (rows are cut into contiguous chunks of
+ * c = 8 ceil(N / 16384); a chunk adds, for each of 4 interleaved row-pair streams, its terms in ascending order, then
+ * ((s0 + s1) + s2) + s3; eight neighbouring chunks are added in ascending order from 0, then those totals in ascending order);
+ * dev_changed (iters + 1) int32, the rows whose a_n differs from the pass before (before the first pass every row counts as -1):
+ * a pass with changed = 0 is an exact fixed point, and every later pass repeats it; dev_counts (K) int32 rows and dev_wsum (K)
+ * float64 weight (the update's order) of each cluster of the last assignment; dev_nearest (K) int32, the row of each final cluster
+ * with the least d2, ties to the lower row, -1 for a cluster without rows.
+ * Where rows, centres and weights are small integers nothing rounds, and everything equals a-link_amd/cluster.py: kmeans (host
+ * float64) bit for bit.  Results are bit-identical from run to run: no floating-point atomics.  The call enqueues at most 6
+ * launches per pass on `stream` and returns: no host synchronisation, nothing read back.  The (N x K) scores never exist in
+ * memory.  ALINK_EINVAL, nothing launched and no output touched: dev_x, dev_centres, dev_assign or dev_scratch NULL, a pair form
+ * without dev_r / dev_ri, N outside 1 .. 2^31 - 1, D outside 1 .. 8192, K outside 1 .. 8192, iters < 0, dev_scratch not 256-byte
+ * aligned.  dev_scratch >= alink_kmeans_scratch_bytes(N, D, K) (0 for sizes the call refuses).  Not here: several ranks' pools in
+ * one call, a cosine metric, relocating empty clusters, mini-batch k-means, an early return once changed = 0. */
+size_t alink_kmeans_scratch_bytes(int64_t N, int D, int K);
+int alink_kmeans(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                 const float* dev_weight, float* dev_centres, int K, int iters,
+                 int32_t* dev_assign, float* dev_d2, double* dev_inertia, int32_t* dev_changed,
+                 int32_t* dev_counts, double* dev_wsum, int32_t* dev_nearest,
+                 void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

@@ -1200,15 +1200,8 @@ struct ConvExtras {
     int splitk = 1;               // > 1: f32 slabs + launch_conv_split_finish
     int nprod = 0;                // split precision: 3 (0 = 3) or 1
     int* kernel = nullptr;        // out: the ConvKernel chosen
-    int* form = nullptr;          // out: 0 = that kernel, 1 = conv3x3_lat_kernel, 2 = conv_gemm_lat_kernel
+    int* form = nullptr;          // out: served_form (net_host.h) of the launch
 };
-
-// Which kernel serves launch_conv(k, dtype, q): the launchers' own hand-off predicates on the ConvParams that is launched.
-static int served_form(ConvKernel k, int dtype, const ConvParams& q) {
-    if (k == ConvKernel::Igemm) return conv_gemm_lat_applies(dtype, q) ? 2 : 0;          // launch_conv_igemm
-    if (traits(k).channel_block) return conv3x3_lat_applies(dtype, q) ? 1 : 0;           // launch_conv3x3_linear
-    return 0;
-}
 
 // Requests the entries turn down before anything is allocated: what a launcher would refuse, and what one would ignore.
 static int check_extras(ConvKernel kernel, int dtype, int ksz, int Cin, const float* dev_alpha, const void* dev_resid,

@@ -206,6 +206,14 @@ inline hipError_t launch_conv_maybe_split(ConvKernel kernel, int dtype, const Co
     return e;
 }
 
+// Which kernel serves launch_conv(k, dtype, q): the launchers' own hand-off predicates on the ConvParams that is launched.
+// 0 = kernel k itself, 1 = conv3x3_lat_kernel, 2 = conv_gemm_lat_kernel.
+inline int served_form(ConvKernel k, int dtype, const ConvParams& q) {
+    if (k == ConvKernel::Igemm) return conv_gemm_lat_applies(dtype, q) ? 2 : 0;          // launch_conv_igemm
+    if (traits(k).channel_block) return conv3x3_lat_applies(dtype, q) ? 1 : 0;           // launch_conv3x3_linear
+    return 0;
+}
+
 // ---- per-launch timing ----------------------------------------------------------------------------------------------------
 // Events around the launches of a profiled call; destroyed with the object on every return path.
 class LaunchTimer {

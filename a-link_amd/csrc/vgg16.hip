@@ -164,7 +164,7 @@ int alink_vgg16_finalize(alink_vgg16_t* r) {
             r->buf_elems_per_image = std::max(r->buf_elems_per_image, (size_t)H * W * cout);
             cin = cout;
         }
-        VOp mp; mp.kind = 2; mp.in_buf = cur; mp.out_buf = cur ^ 1; mp.H = H; mp.W = W; mp.C = cin; mp.name = "pool";
+        VOp mp; mp.kind = 2; mp.in_buf = cur; mp.out_buf = cur ^ 1; mp.H = H; mp.W = W; mp.C = cin; mp.name = "pool" + std::to_string(b + 1);
         cur ^= 1;
         r->ops.push_back(mp);
         H /= 2; W /= 2;
@@ -180,19 +180,14 @@ size_t alink_vgg16_workspace_bytes(const alink_vgg16_t* r, int n_images) {
     return 2 * one;
 }
 
-int alink_vgg16_embed(alink_vgg16_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
-                      size_t ws_bytes, void* stream) {
-    ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_vgg16_embed before finalize");
-    DeviceGuard dg(r->device);
-    ALINK_REQUIRE(dev_in && dev_out && ws && n > 0, ALINK_EINVAL, "bad argument");
-    ALINK_REQUIRE(((uintptr_t)ws & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
-    ALINK_REQUIRE(ws_bytes >= alink_vgg16_workspace_bytes(r, n), ALINK_ENOMEM, "workspace too small");
-    ALINK_REQUIRE((long long)n * r->buf_elems_per_image < (1ll << 31), ALINK_EINVAL, "batch of %d too large; split it", n);
-    hipStream_t st = (hipStream_t)stream;
+// ops [0, n_ops) of the network on the caller's workspace: alink_vgg16_embed's whole forward (n_ops = all of them) and the
+// prefixes alink_debug_vgg16_embed_prefix stops at are this one loop.  The arguments are already checked.
+static int run_ops(alink_vgg16* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws, size_t n_ops,
+                   hipStream_t st) {
     const size_t one = ((size_t)n * r->buf_elems_per_image * 2 + 255) & ~(size_t)255;
     auto buf = [&](int id) -> void* { return (char*)ws + one * id; };
     const size_t nops = r->ops.size();
-    for (size_t i = 0; i < nops; ++i) {
+    for (size_t i = 0; i < n_ops; ++i) {
         const VOp& op = r->ops[i];
         if (op.kind == 0) {
             StemParams sp{};
@@ -220,6 +215,55 @@ int alink_vgg16_embed(alink_vgg16_t* r, const float* dev_in, int n, int preproce
         ALINK_HIP(hipGetLastError());
     }
     return ALINK_OK;
+}
+
+// the argument checks of a forward over n images (after the handle's own); need_out: the last pool runs, which writes dev_out
+static int check_forward_args(alink_vgg16* r, const float* dev_in, int n, const float* dev_out, bool need_out, const void* ws,
+                              size_t ws_bytes) {
+    ALINK_REQUIRE(dev_in && (dev_out || !need_out) && ws && n > 0, ALINK_EINVAL, "bad argument");
+    ALINK_REQUIRE(((uintptr_t)ws & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
+    ALINK_REQUIRE(ws_bytes >= alink_vgg16_workspace_bytes(r, n), ALINK_ENOMEM, "workspace too small");
+    ALINK_REQUIRE((long long)n * r->buf_elems_per_image < (1ll << 31), ALINK_EINVAL, "batch of %d too large; split it", n);
+    return ALINK_OK;
+}
+
+int alink_vgg16_embed(alink_vgg16_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
+                      size_t ws_bytes, void* stream) {
+    ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_vgg16_embed before finalize");
+    DeviceGuard dg(r->device);
+    const int rc = check_forward_args(r, dev_in, n, dev_out, true, ws, ws_bytes);
+    if (rc) return rc;
+    return run_ops(r, dev_in, n, preprocessed, dev_out, ws, r->ops.size(), (hipStream_t)stream);
+}
+
+// diagnostic (include/alink_hip_debug.h): the forward stopped after its first n_ops ops, and where and what op n_ops - 1 wrote
+int alink_debug_vgg16_embed_prefix(alink_vgg16_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
+                                   size_t ws_bytes, void* stream, int n_ops, size_t* byte_offset, int* H, int* W, int* C,
+                                   char* name_buf, int name_len, int* kernel, int* form) {
+    if (!r || !r->finalized) { set_error("alink_debug_vgg16_embed_prefix before finalize"); return -1; }
+    const int nops = (int)r->ops.size();
+    if (n_ops <= 0) return nops;
+    if (n_ops > nops) { set_error("the network has %d ops, asked for %d", nops, n_ops); return -1; }
+    DeviceGuard dg(r->device);
+    if (check_forward_args(r, dev_in, n, dev_out, n_ops == nops, ws, ws_bytes)) return -1;
+    const VOp& op = r->ops[n_ops - 1];
+    const size_t one = ((size_t)n * r->buf_elems_per_image * 2 + 255) & ~(size_t)255;
+    if (byte_offset) *byte_offset = n_ops == nops ? 0 : one * op.out_buf;
+    if (H) *H = op.kind == 0 ? r->H : (op.kind == 1 ? op.cp.Ho : op.H / 2);
+    if (W) *W = op.kind == 0 ? r->W : (op.kind == 1 ? op.cp.Wo : op.W / 2);
+    if (C) *C = op.kind == 0 ? 64 : (op.kind == 1 ? op.cp.Cout : op.C);
+    if (name_buf && name_len > 0) snprintf(name_buf, (size_t)name_len, "%s", op.name.c_str());
+    if (kernel) *kernel = op.kind == 1 ? (int)op.kernel : -1;
+    if (form) {
+        *form = 0;
+        if (op.kind == 1) {
+            ConvParams p = op.cp;
+            with_batch(p, n);
+            *form = served_form(op.kernel, r->dtype, p);
+        }
+    }
+    if (run_ops(r, dev_in, n, preprocessed, dev_out, ws, (size_t)n_ops, (hipStream_t)stream)) return -1;
+    return nops;
 }
 
 }  // extern "C"

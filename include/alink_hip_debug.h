@@ -113,6 +113,21 @@ int alink_debug_resnet50_grad_cache_info(const struct alink_resnet50* r, int n_i
 int alink_debug_backbone_grad_cache_info(const struct alink_backbone* bb, int n_images, int index, size_t* byte_offset, int* H,
                                          int* W, int* C, char* name_buf, int name_len);
 
+/* ---- the VGG-16 forward stopped early (csrc/vgg16.hip) ------------------------------------------------------------------- */
+/* alink_vgg16_embed's own op loop, run for ops [0, n_ops) only, on the caller's workspace: the arguments of alink_vgg16_embed,
+ * then n_ops and what op n_ops - 1 wrote.  The network is 18 ops in execution order: "conv1_1" (the stem), twelve
+ * convolutions "convB_L" and the five pools "pool1" .. "pool5", each behind its block.  Reported for op n_ops - 1: the byte
+ * offset of its output from the workspace pointer, its shape [n_images][H][W][C] in the handle's 16-bit type, its name, the
+ * ConvKernel chosen at finalize (csrc/conv_kernel.h; -1 for the stem and the pools) and the form that serves this launch, by
+ * the rule alink_conv_nhwc_ex reports by (0 = that kernel, 1 = conv3x3_lat_kernel, 2 = conv_gemm_lat_kernel).  With
+ * n_ops = 18 the output is the float32 features in dev_out ([n_images][H * W * C]; byte_offset is 0); a shorter prefix does
+ * not touch dev_out, which may then be NULL.  Any out pointer may be NULL.  Returns the number of ops, or -1 with
+ * alink_last_error set; with n_ops <= 0 nothing is launched and nothing filled.  Tests only (tests/test_gpu_vgg16.py). */
+struct alink_vgg16;
+int alink_debug_vgg16_embed_prefix(struct alink_vgg16* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,
+                                   void* ws, size_t ws_bytes, void* stream, int n_ops, size_t* byte_offset, int* H, int* W,
+                                   int* C, char* name_buf, int name_len, int* kernel, int* form);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,10 @@ PROTOTYPES = {
     "alink_kmeanspp": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "alink_kmeans_scratch_bytes": (_sz, [_i64, _i, _i]),
     "alink_kmeans": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i] + [_vp] * 7 + [_vp, _vp]),
+    "alink_knn_scratch_bytes": (_sz, [_i64, _i, _i]),
+    "alink_knn": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, C.c_double] + [_vp] * 4 + [_vp, _vp]),
+    "alink_group_argmax_scratch_bytes": (_sz, [_i64, _i]),
+    "alink_group_argmax": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

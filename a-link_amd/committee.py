@@ -185,6 +185,18 @@ class Bagging:
         return _cluster.diverse_minibatch_device((emb_left, emb_right, li, ri), utility, n_instances, beta=beta, iters=iters,
                                                  uniforms=uniforms, seed=seed)
 
+    def typiclust_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, k_nn=20, min_cluster_size=5, max_clusters=500,
+                          iters=10, uniforms=None, seed=None):
+        """Extension: TypiClust queries (typiclust.py; Hacohen et al. 2022) among the pairs (li[p], ri[p]) gathered from ONE left
+        and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs (indices into
+        li / ri) that are labelled already.  The members are not consulted: the strategy needs no scorer.
+        -> (picks int64 NumPy array, info), typiclust.typiclust_device's."""
+        from . import typiclust as _typiclust
+        self._one_feature_space(emb_left, emb_right)
+        return _typiclust.typiclust_device((emb_left, emb_right, li, ri), labelled, n_instances, k_nn=k_nn,
+                                           min_cluster_size=min_cluster_size, max_clusters=max_clusters, iters=iters, uniforms=uniforms,
+                                           seed=seed)
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

@@ -1,0 +1,421 @@
+// knn.hip — the K nearest neighbours of every pool row among the pool's other rows, their distances and the typicality of
+// TypiClust (Hacohen, Dekel & Weinshall 2022: the inverse of the mean distance to the K nearest neighbours), and the per-group
+// argmax that turns typicalities into queries (a-link_amd/typiclust.py).  include/alink_hip.h (alink_knn, alink_group_argmax)
+// states the rule in full.
+//
+// What bounds it: an (N x D)(D x N) product on the f32 matrix cores whose scores never reach memory — km_assign_kernel
+// (kmeans.hip) with the pool as its own centres and a running sorted list of K in place of a running minimum.
+// v_mfma_f32_32x32x2_f32 is bit for bit an ascending fmaf chain, so x_n . x_j is ONE chain over e = 0 .. D - 1 from 0 whatever tile
+// either row falls in.
+//
+// Launches of alink_knn, all on the caller's stream, whose order is the ONLY ordering between workgroups (no cooperative launch,
+// no grid barrier, no atomics, nothing read back):
+//   kn_norm_kernel  |x_j|^2 of every row, one wave per row, in the summation order of batch_rows.h
+//   kn_list_kernel  workgroup = 128 rows (4 waves x 32), walks the pool in tiles of 128 candidates (4 MFMA row blocks of 32 per
+//                   wave).  Both operands go through LDS in chunks of 32 columns, stored column-major; the pair form takes |l - r|
+//                   while staging; the tile's norms and groups lie beside them.  MFMA M = candidates, N = rows: lane (l, h) of a
+//                   wave holds for row l the 16 candidates (r & 3) + 8 (r >> 2) + 4 h of each block — ascending in r, so a strict
+//                   `<` keeps the lower candidate among ties.  The lane's running KK best are a sorted list of (score, index) in
+//                   registers (KK = 8 / 16 / 32 at compile time, every index a constant: a smaller K is the head of the next larger
+//                   list); a candidate enters through an unrolled compare-and-shift chain, which only those candidates walk that
+//                   SOME lane of the wave holds below its KK-th — a wave-uniform vote per candidate, gathered into a 16-bit mask per
+//                   MFMA block and worked off in ascending order, so the chain stands four times in the code, not 64.  At the end
+//                   the two lanes of a row exchange their lists with lane ^ 32 and merge them on (score, index): min(A[i],
+//                   B[KK - 1 - i]) is a bitonic sequence of the KK least, log2(KK) half-cleaner stages sort it.
+//   kn_dist_kernel  the light pass, one wave per row: d2 of the K winners by direct differences in batch_rows.h's order, and the
+//                   float64 mean of the typicality in ascending slot order.
+// alink_group_argmax is two launches in the shape of km_accum_kernel / km_final_kernel: wave (g, s) scans slice s of the group
+// vector in ascending row order, then one thread per group combines the slices in ascending order.
+// Measured: DESIGN.md §9.  Not built: skipping candidate tiles that hold no row of the workgroup's groups, a rectangular form
+// (queries against a separate reference set), K > 32, a cosine metric, several ranks' pools in one call.
+#include "batch_rows.h"
+
+namespace alink {
+namespace {
+
+constexpr int KN_MAX_K = 32;
+constexpr int KN_MAX_G = 8192;
+constexpr int KN_TN = 128;                 // rows of a workgroup: 32 per wave
+constexpr int KN_TK = 128;                 // candidates of a tile: four MFMA row blocks per wave
+constexpr int KN_DC = 32;                  // columns of a chunk in LDS
+constexpr int KN_LD = KN_TN + 4;           // LDS row pitch (floats): column e of the tile at e * KN_LD
+constexpr int KN_SLICE_ALIGN = 256;
+
+__device__ __forceinline__ float kn_wave_sum(float s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
+// |x_n|^2: the squared distance of row n to the zero row in the order of batch_rows.h.  One wave per row.
+template <bool PAIR, bool VEC>
+__global__ __launch_bounds__(256) void kn_norm_kernel(const RbRows t, long long N, float* __restrict__ xnorm) {
+    const int lane = threadIdx.x & 63;
+    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const RbRow r = rb_row<PAIR>(t, n);
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float s = 0.f;
+    for (int e0 = 4 * lane; e0 < t.D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, t.D), zero);
+    s = kn_wave_sum(s);
+    if (lane == 0) xnorm[n] = s;
+}
+
+// columns e0 .. e0 + 3 of a tile row; absent rows and columns are zeros
+template <bool PAIR, bool VEC>
+__device__ __forceinline__ float4 kn_fetch(const RbRows& t, long long n, bool have, int e0) {
+    if (!have || e0 >= t.D) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return rb_quad<PAIR, VEC>(rb_row<PAIR>(t, n), e0, t.D);
+}
+
+// a candidate of a lane's own stream (ascending index) into its sorted list: strict `<`, so it lands behind its equals
+template <int KK>
+__device__ __forceinline__ void kn_insert(float (&ls)[KK], int (&lj)[KK], float s, int j) {
+#pragma unroll
+    for (int p = KK - 1; p > 0; --p) {
+        const bool up = s < ls[p - 1], here = s < ls[p];
+        ls[p] = up ? ls[p - 1] : (here ? s : ls[p]);
+        lj[p] = up ? lj[p - 1] : (here ? j : lj[p]);
+    }
+    const bool first = s < ls[0];
+    ls[0] = first ? s : ls[0];
+    lj[0] = first ? j : lj[0];
+}
+// element r (uniform over the wave) of 16 registers, by a tree of selects: no index reaches the array at run time
+template <int LO, int CNT>
+__device__ __forceinline__ float kn_pick(const float (&v)[16], int r) {
+    if constexpr (CNT == 1) {
+        return v[LO];
+    } else {
+        const float lo = kn_pick<LO, CNT / 2>(v, r), hi = kn_pick<LO + CNT / 2, CNT / 2>(v, r);
+        return (r & (CNT / 2)) ? hi : lo;
+    }
+}
+__device__ __forceinline__ float kn_pick16(const float (&v)[16], int r) { return kn_pick<0, 16>(v, r); }
+
+// (score, index) order; an empty slot is (+inf, -1), behind every real entry (whose score is below +inf)
+__device__ __forceinline__ bool kn_less(float sa, int ja, float sb, int jb) { return sa < sb || (sa == sb && ja < jb); }
+
+// the two sorted lists of a row's two lanes -> the KK least of both, sorted, in both lanes.  min(A[i], B[KK - 1 - i]) over i holds
+// the KK least of the union as a bitonic sequence; log2(KK) half-cleaner stages sort it.  Every index is a constant.
+template <int KK>
+__device__ __forceinline__ void kn_merge_halves(float (&ls)[KK], int (&lj)[KK]) {
+    float os[KK];
+    int oj[KK];
+#pragma unroll
+    for (int p = 0; p < KK; ++p) { os[p] = __shfl_xor(ls[KK - 1 - p], 32, 64); oj[p] = __shfl_xor(lj[KK - 1 - p], 32, 64); }
+#pragma unroll
+    for (int p = 0; p < KK; ++p) {
+        const bool take = kn_less(os[p], oj[p], ls[p], lj[p]);
+        ls[p] = take ? os[p] : ls[p];
+        lj[p] = take ? oj[p] : lj[p];
+    }
+#pragma unroll
+    for (int st = KK / 2; st > 0; st >>= 1) {
+#pragma unroll
+        for (int p = 0; p < KK; ++p) {
+            if ((p & st) == 0) {
+                const bool swap = kn_less(ls[p + st], lj[p + st], ls[p], lj[p]);
+                const float s0 = ls[p], s1 = ls[p + st];
+                const int j0 = lj[p], j1 = lj[p + st];
+                ls[p] = swap ? s1 : s0; ls[p + st] = swap ? s0 : s1;
+                lj[p] = swap ? j1 : j0; lj[p + st] = swap ? j0 : j1;
+            }
+        }
+    }
+}
+
+// Two waves per SIMD, as the assignment kernel has: asked for, because left alone the compiler spends 255 + 80 registers at
+// KK = 32 and fits one.  The one form that does not fit 256 registers without scratch — KK = 32 on a row table read with scalar
+// loads — keeps one wave.
+template <int KK, bool PAIR, bool VEC>
+__global__ __launch_bounds__(256, (KK == 32 && !PAIR && !VEC) ? 1 : 2) void kn_list_kernel(const RbRows t, long long N, const float* __restrict__ xnorm,
+                                                      const int32_t* __restrict__ group, int K, int32_t* __restrict__ idx,
+                                                      int32_t* __restrict__ found) {
+    __shared__ float sX[KN_DC * KN_LD];
+    __shared__ float sC[KN_DC * KN_LD];
+    __shared__ __attribute__((aligned(16))) float sN[KN_TK];
+    __shared__ __attribute__((aligned(16))) int sG[KN_TK];
+    const int D = t.D;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
+    const long long n0 = (long long)blockIdx.x * KN_TN;
+    // staging: thread -> tile row (tid & 127), column quads (tid >> 7) + 2 q, q = 0 .. 3
+    const int srow = tid & 127, sq0 = tid >> 7;
+    const long long xn = n0 + srow;
+    const bool xhave = xn < N;
+
+    // this lane's row: its index, and its group — -2, which no candidate carries (no neighbours), past the pool, in a group < 0, or
+    // with |x|^2 NaN or +inf
+    const long long n = n0 + wave * 32 + l31;
+    int gn = -2;
+    if (n < N) {
+        gn = group ? group[n] : 0;
+        if (gn < 0 || !(xnorm[n] < INFINITY)) gn = -2;
+    }
+    const int self = n < N ? (int)n : -1;
+
+    float ls[KK];                          // a score enters by `<` alone: neither NaN nor +inf ever does
+    int lj[KK];
+#pragma unroll
+    for (int p = 0; p < KK; ++p) { ls[p] = INFINITY; lj[p] = -1; }
+
+    for (long long k0 = 0; k0 < N; k0 += KN_TK) {
+        const long long left = N - k0;
+        const int nblk = left >= KN_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
+        const long long cn_ = k0 + srow;
+        const bool chave = cn_ < N;
+        f32x16 acc[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
+        for (int d0 = 0; d0 < D; d0 += KN_DC) {
+            float4 vx[4], vc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e0 = d0 + 4 * (sq0 + 2 * q);
+                vx[q] = kn_fetch<PAIR, VEC>(t, xn, xhave, e0);
+                vc[q] = kn_fetch<PAIR, VEC>(t, cn_, chave, e0);
+            }
+            __syncthreads();                               // the previous chunk's operands (and the tile's norms, groups) are read
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = 4 * (sq0 + 2 * q);
+                sX[(c + 0) * KN_LD + srow] = vx[q].x; sX[(c + 1) * KN_LD + srow] = vx[q].y;
+                sX[(c + 2) * KN_LD + srow] = vx[q].z; sX[(c + 3) * KN_LD + srow] = vx[q].w;
+                sC[(c + 0) * KN_LD + srow] = vc[q].x; sC[(c + 1) * KN_LD + srow] = vc[q].y;
+                sC[(c + 2) * KN_LD + srow] = vc[q].z; sC[(c + 3) * KN_LD + srow] = vc[q].w;
+            }
+            if (d0 == 0 && tid < KN_TK) {
+                const long long j = k0 + tid;
+                sN[tid] = j < N ? xnorm[j] : INFINITY;     // a padded candidate never enters
+                const int gj = j < N ? (group ? group[j] : 0) : -1;
+                sG[tid] = gj < 0 ? -1 : gj;                // every group < 0 is -1 here: nobody's neighbour
+            }
+            __syncthreads();
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                float xv[8], cv[4][8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int e = 16 * half + 2 * i + hh;
+                    xv[i] = sX[e * KN_LD + wave * 32 + l31];
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) cv[b][i] = sC[e * KN_LD + b * 32 + l31];
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (b < nblk) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[b][i], xv[i], acc[b], 0, 0, 0);
+                }
+            }
+        }
+        // the tile's scores against the running list: in a lane the candidates come in ascending order
+        const int jbase = (int)(unsigned)k0 + 4 * hh;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            if (b < nblk) {
+                // the block's 16 scores of this lane, and which of them SOME lane of the wave holds below its KK-th (uniform): only
+                // those walk the insertion chain, in ascending order.  (A list's KK-th only falls, so a candidate that is not
+                // marked against the KK-th of before the block's insertions would not have entered after them either, and a
+                // marked one that no longer enters leaves the list as it is.)
+                float sc[16];
+                unsigned marked = 0;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 cn = *(const float4*)(sN + b * 32 + 8 * g + 4 * hh);
+                    const int4 cg = *(const int4*)(sG + b * 32 + 8 * g + 4 * hh);
+                    const float cnv[4] = {cn.x, cn.y, cn.z, cn.w};
+                    const int cgv[4] = {cg.x, cg.y, cg.z, cg.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int j = jbase + b * 32 + 8 * g + i;
+                        const float s = __builtin_fmaf(-2.f, acc[b][4 * g + i], cnv[i]);
+                        sc[4 * g + i] = (cgv[i] == gn && j != self) ? s : INFINITY;
+                        marked |= __ballot(sc[4 * g + i] < ls[KK - 1]) != 0ull ? 1u << (4 * g + i) : 0u;
+                    }
+                }
+#pragma unroll 1
+                while (marked) {
+                    const int r = __ffs(marked) - 1;
+                    marked &= marked - 1;
+                    kn_insert<KK>(ls, lj, kn_pick16(sc, r), jbase + b * 32 + 8 * (r >> 2) + (r & 3));
+                }
+            }
+        }
+    }
+    kn_merge_halves<KK>(ls, lj);           // the two halves of a row meet
+    if (hh == 0 && n < N) {
+        int32_t* o = idx + (size_t)n * K;
+        int f = 0;
+#pragma unroll
+        for (int p = 0; p < KK; ++p)
+            if (p < K) { o[p] = lj[p]; f += lj[p] >= 0; }
+        if (found) found[n] = f;
+    }
+}
+
+// the light pass, one wave per row: d2 of the winners, the typicality
+template <bool PAIR, bool VEC>
+__global__ __launch_bounds__(256) void kn_dist_kernel(const RbRows t, long long N, int K, const int32_t* __restrict__ idx, int squared,
+                                                      double eps, float* __restrict__ d2, float* __restrict__ typicality) {
+    const int D = t.D;
+    const int lane = threadIdx.x & 63;
+    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const RbRow r = rb_row<PAIR>(t, n);
+    double sum = 0.0;                                      // the found slots in ascending order (every lane holds the same)
+    int f = 0;
+    for (int p = 0; p < K; ++p) {
+        const int j = idx[(size_t)n * K + p];
+        float d = __builtin_nanf("");
+        if (j >= 0) {                                      // (uniform over the wave)
+            const RbRow c = rb_row<PAIR>(t, j);
+            float s = 0.f;
+            for (int e0 = 4 * lane; e0 < D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, D), rb_quad<PAIR, VEC>(c, e0, D));
+            d = kn_wave_sum(s);
+            sum += squared ? (double)d : sqrt((double)d);
+            ++f;
+        }
+        if (lane == 0 && d2) d2[(size_t)n * K + p] = d;
+    }
+    if (lane == 0 && typicality) typicality[n] = f ? (float)(1.0 / (sum / (double)f + eps)) : 0.f;
+}
+
+// slices of the group scan: a function of (N, G) alone (the rule of the k-means update).  *len = rows of a slice -> their number
+__host__ __device__ __forceinline__ int ga_slices(long long N, int G, long long* len) {
+    long long S = G >= 2048 ? 1 : (4096 + G - 1) / G;
+    if (S > 64) S = 64;
+    long long L = (N + S - 1) / S;
+    L = (L + KN_SLICE_ALIGN - 1) / KN_SLICE_ALIGN * KN_SLICE_ALIGN;
+    *len = L;
+    return (int)((N + L - 1) / L);
+}
+
+// wave (g, s): the rows of group g in slice s, ascending; the largest value by `>` from -inf, ties to the lower row
+__global__ __launch_bounds__(64) void ga_scan_kernel(const float* __restrict__ value, const int32_t* __restrict__ group, long long N,
+                                                     long long slice, int S, float* __restrict__ pval, int32_t* __restrict__ prow) {
+    const int lane = threadIdx.x, g = blockIdx.x, s = blockIdx.y;
+    const long long r0 = (long long)s * slice, r1 = r0 + slice < N ? r0 + slice : N;
+    float bv = -INFINITY;
+    int br = -1;
+    for (long long base = r0; base < r1; base += 64) {
+        const long long n = base + lane;
+        if (n < r1 && group[n] == g) {
+            const float v = value[n];
+            if (v > bv) { bv = v; br = (int)n; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int orow = __shfl_xor(br, o, 64);
+        if (orow >= 0 && (br < 0 || ov > bv || (ov == bv && orow < br))) { bv = ov; br = orow; }
+    }
+    if (lane == 0) { pval[(size_t)g * S + s] = bv; prow[(size_t)g * S + s] = br; }
+}
+
+// one thread per group: the slices' winners in ascending order
+__global__ __launch_bounds__(256) void ga_final_kernel(int G, int S, const float* __restrict__ pval, const int32_t* __restrict__ prow,
+                                                       int32_t* __restrict__ best) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= G) return;
+    float bv = -INFINITY;
+    int br = -1;
+    for (int s = 0; s < S; ++s) {
+        const float v = pval[(size_t)g * S + s];
+        const int r = prow[(size_t)g * S + s];
+        if (r >= 0 && v > bv) { bv = v; br = r; }
+    }
+    best[g] = br;
+}
+
+size_t kn_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct KnArgs {
+    const int32_t* group;
+    int K, squared;
+    double eps;
+    int32_t* idx;
+    float* d2;
+    int32_t* found;
+    float* typicality;
+};
+
+template <bool PAIR, bool VEC>
+void kn_enqueue(const RbRows& t, long long N, const KnArgs& a, float* xnorm, hipStream_t st) {
+    const unsigned wgrid = (unsigned)((N + 3) / 4);
+    const unsigned lgrid = (unsigned)((N + KN_TN - 1) / KN_TN);
+    hipLaunchKernelGGL((kn_norm_kernel<PAIR, VEC>), dim3(wgrid), dim3(256), 0, st, t, N, xnorm);
+    if (a.K <= 8)
+        hipLaunchKernelGGL((kn_list_kernel<8, PAIR, VEC>), dim3(lgrid), dim3(256), 0, st, t, N, xnorm, a.group, a.K, a.idx, a.found);
+    else if (a.K <= 16)
+        hipLaunchKernelGGL((kn_list_kernel<16, PAIR, VEC>), dim3(lgrid), dim3(256), 0, st, t, N, xnorm, a.group, a.K, a.idx, a.found);
+    else
+        hipLaunchKernelGGL((kn_list_kernel<32, PAIR, VEC>), dim3(lgrid), dim3(256), 0, st, t, N, xnorm, a.group, a.K, a.idx, a.found);
+    if (a.d2 || a.typicality)
+        hipLaunchKernelGGL((kn_dist_kernel<PAIR, VEC>), dim3(wgrid), dim3(256), 0, st, t, N, a.K, a.idx, a.squared, a.eps, a.d2,
+                           a.typicality);
+}
+
+}  // namespace
+}  // namespace alink
+
+using namespace alink;
+
+extern "C" {
+
+size_t alink_knn_scratch_bytes(int64_t N, int D, int K) {
+    if (N <= 0 || N >= (1ll << 31) || D <= 0 || D > RB_MAX_D || K <= 0 || K > KN_MAX_K) return 0;
+    return kn_align((size_t)N * 4);
+}
+
+int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+              const int32_t* dev_group, int K, int squared, double eps, int32_t* dev_idx, float* dev_d2, int32_t* dev_found,
+              float* dev_typicality, void* dev_scratch, void* stream) {
+    ALINK_REQUIRE(dev_x && dev_idx && dev_scratch, ALINK_EINVAL, "NULL argument");
+    ALINK_REQUIRE(!dev_li || (dev_r && dev_ri), ALINK_EINVAL, "the pair form needs dev_r and dev_ri beside dev_li");
+    ALINK_REQUIRE(N >= 1 && N < (1ll << 31), ALINK_EINVAL, "N=%lld outside 1..2^31-1", (long long)N);
+    ALINK_REQUIRE(D >= 1 && D <= RB_MAX_D, ALINK_EINVAL, "D=%d outside 1..%d", D, RB_MAX_D);
+    ALINK_REQUIRE(K >= 1 && K <= KN_MAX_K, ALINK_EINVAL, "K=%d outside 1..%d", K, KN_MAX_K);
+    ALINK_REQUIRE(((uintptr_t)dev_scratch & 255) == 0, ALINK_EINVAL, "scratch must be 256-byte aligned");
+    DeviceGuard dg(device_of_pointer(dev_x));
+    RbRows t{dev_x, dev_r, dev_li, dev_ri, D};
+    const KnArgs a{dev_group, K, squared ? 1 : 0, eps, dev_idx, dev_d2, dev_found, dev_typicality};
+    hipStream_t st = (hipStream_t)stream;
+    const bool pair = dev_li != nullptr;
+    const bool vec = D % 4 == 0 && (((uintptr_t)dev_x | (pair ? (uintptr_t)dev_r : 0)) & 15) == 0;
+    float* xnorm = (float*)dev_scratch;
+    if (pair) { if (vec) kn_enqueue<true, true>(t, N, a, xnorm, st); else kn_enqueue<true, false>(t, N, a, xnorm, st); }
+    else { if (vec) kn_enqueue<false, true>(t, N, a, xnorm, st); else kn_enqueue<false, false>(t, N, a, xnorm, st); }
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+size_t alink_group_argmax_scratch_bytes(int64_t N, int G) {
+    if (N <= 0 || N >= (1ll << 31) || G <= 0 || G > KN_MAX_G) return 0;
+    long long slice;
+    const size_t S = (size_t)ga_slices(N, G, &slice);
+    return kn_align((size_t)G * S * 4) * 2;
+}
+
+int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t N, int G, int32_t* dev_best, void* dev_scratch,
+                       void* stream) {
+    ALINK_REQUIRE(dev_value && dev_group && dev_best && dev_scratch, ALINK_EINVAL, "NULL argument");
+    ALINK_REQUIRE(N >= 1 && N < (1ll << 31), ALINK_EINVAL, "N=%lld outside 1..2^31-1", (long long)N);
+    ALINK_REQUIRE(G >= 1 && G <= KN_MAX_G, ALINK_EINVAL, "G=%d outside 1..%d", G, KN_MAX_G);
+    ALINK_REQUIRE(((uintptr_t)dev_scratch & 255) == 0, ALINK_EINVAL, "scratch must be 256-byte aligned");
+    DeviceGuard dg(device_of_pointer(dev_value));
+    long long slice;
+    const int S = ga_slices(N, G, &slice);
+    float* pval = (float*)dev_scratch;
+    int32_t* prow = (int32_t*)((char*)dev_scratch + kn_align((size_t)G * S * 4));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ga_scan_kernel, dim3(G, S), dim3(64), 0, st, dev_value, dev_group, (long long)N, slice, S, pval, prow);
+    hipLaunchKernelGGL(ga_final_kernel, dim3((G + 255) / 256), dim3(256), 0, st, G, S, pval, prow, dev_best);
+    ALINK_HIP(hipGetLastError());
+    return ALINK_OK;
+}
+
+}  // extern "C"

@@ -752,6 +752,55 @@ int alink_kmeans(const float* dev_x, const float* dev_r, const int32_t* dev_li, 
                  int32_t* dev_assign, float* dev_d2, double* dev_inertia, int32_t* dev_changed,
                  int32_t* dev_counts, double* dev_wsum, int32_t* dev_nearest,
                  void* dev_scratch, void* stream);
+/* EXTENSION — the K nearest neighbours of every pool row among the pool's other rows, their squared distances
+ * and the typicality of TypiClust (Hacohen, Dekel & Weinshall 2022; a-link_amd/typiclust.py).  The pool as alink_kmeans takes it: an
+ * (N, D) row table dev_x (dev_li == NULL), or row n = |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the fly.  dev_group: (N) int32
+ * or NULL (every row in group 0).  The rule:
+ *   candidates  of row n: every j != n of the same group.  A row of group < 0 has no neighbours and is nobody's neighbour, and so
+ *               has a row whose |x|^2 (below) is NaN or +inf.  Duplicate rows are neighbours at distance 0.  Passing alink_kmeans'
+ *               dev_assign as dev_group makes "the neighbours inside a row's own cluster" one call.
+ *   score       dot(n, j) = x_n . x_j — float32, ONE fused multiply-add per element from 0 in ascending element order e = 0 .. D - 1,
+ *               the chain of alink_kmeans (what one MFMA accumulator gives: a function of D alone);  xn_j = |x_j|^2 — float32, the
+ *               squared distance of x_j to the zero row in alink_ranked_batch's order (element e to lane (e / 4) % 64, one fused
+ *               multiply-add each, ascending per lane, an xor butterfly over the 64 lanes);  score(n, j) = fmaf(-2, dot(n, j), xn_j),
+ *               one rounding.  A score that is NaN or +inf never enters a list.
+ *   list        row n's neighbours are the K candidates of least (score, index) in lexicographic order, written in that order: ties
+ *               go to the lower index.  dev_found[n] = how many there are (<= K); unfilled slots hold index -1 and d2 = NaN.
+ *   distance    d2(n, slot) = |x_n - x_j|^2 for the K winners only — float32, direct differences in alink_ranked_batch's order
+ *               above: never negative, and the number the ranked batch, information density, k-means++ and k-means report.  The
+ *               ORDER of a list is the score's, not d2's: score(n, j) + |x_n|^2 and d2 round differently, so two neighbours whose
+ *               distances agree to the last bits may stand in d2's reverse order.
+ *   typicality  m_n = (float64 sum over the found slots, in ascending slot order, of sqrt((double)d2)) / found;
+ *               dev_typicality[n] = (float)(1 / (m_n + eps)); 0 for a row with found = 0.  With squared != 0 the term is
+ *               (double)d2 itself: what the public TypiClust code computes, whose index returns squared distances.
+ * Where the rows are small integers nothing rounds, and idx, d2 and found equal a-link_amd/typiclust.py: knn (host float64) bit
+ * for bit.  Results are bit-identical from run to run.  dev_idx (N, K) int32 is required; dev_d2 (N, K) float32, dev_found (N) int32
+ * and dev_typicality (N) float32 may each be NULL.  The call enqueues at most 3 launches on `stream` and returns: no host
+ * synchronisation, no cooperative launch, no grid barrier, no atomics, nothing read back; the (N x N) scores never exist in memory.
+ * ALINK_EINVAL, nothing launched and no output touched: dev_x, dev_idx or dev_scratch NULL, a pair form without dev_r / dev_ri,
+ * N outside 1 .. 2^31 - 1, D outside 1 .. 8192, K outside 1 .. 32, dev_scratch not 256-byte aligned.  dev_scratch >=
+ * alink_knn_scratch_bytes(N, D, K) (0 for sizes the call refuses).  Not here: a rectangular form (queries against a separate
+ * reference set), K > 32, a cosine metric, several ranks' pools in one call, skipping candidate tiles that hold no row of a
+ * workgroup's groups (every workgroup walks the whole pool, with or without dev_group). */
+size_t alink_knn_scratch_bytes(int64_t N, int D, int K);
+int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+              const int32_t* dev_group, int K, int squared, double eps,
+              int32_t* dev_idx,                            /* (N, K) */
+              float* dev_d2,                               /* (N, K) or NULL */
+              int32_t* dev_found,                          /* (N) or NULL */
+              float* dev_typicality,                       /* (N) or NULL */
+              void* dev_scratch, void* stream);
+/* EXTENSION (X12) — per group, the row of the largest value: dev_best[g], g = 0 .. G - 1, = the row n with dev_group[n] == g whose
+ * dev_value[n] is largest by `>` from -inf; ties go to the lower row; NaN and -inf never win; a group without a winner gets -1;
+ * rows whose group is outside 0 .. G - 1 are ignored.  Rows are cut into S slices of L = 256 ceil(ceil(N / S') / 256) rows,
+ * S' = 1 for G >= 2048, else min(64, ceil(4096 / G)), S = ceil(N / L); a wave scans one slice for one group in ascending row order,
+ * the slices' winners are combined in ascending order: no atomics, bit-identical from run to run.  Two launches on `stream`, no
+ * host synchronisation.  ALINK_EINVAL, nothing launched: a NULL argument, N outside 1 .. 2^31 - 1, G outside 1 .. 8192, dev_scratch
+ * not 256-byte aligned.  dev_scratch >= alink_group_argmax_scratch_bytes(N, G) (0 for sizes the call refuses). */
+size_t alink_group_argmax_scratch_bytes(int64_t N, int G);
+int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t N, int G,
+                       int32_t* dev_best,                  /* (G) */
+                       void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

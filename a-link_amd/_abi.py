@@ -195,6 +195,11 @@ PROTOTYPES = {
     "alink_knn": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, C.c_double] + [_vp] * 4 + [_vp, _vp]),
     "alink_group_argmax_scratch_bytes": (_sz, [_i64, _i]),
     "alink_group_argmax": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "alink_ball_scratch_bytes": (_sz, [_i64, _i]),
+    "alink_ball_count": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f] + [_vp] * 3 + [_vp, _vp]),
+    "alink_ball_fill": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "alink_max_coverage_scratch_bytes": (_sz, [_i64, _i]),
+    "alink_max_coverage": (_i, [_vp, _vp, _i64, _vp, _i64, _i] + [_vp] * 3 + [_vp, _vp]),
 }
 
 _lib = None

@@ -197,6 +197,18 @@ class Bagging:
                                            min_cluster_size=min_cluster_size, max_clusters=max_clusters, iters=iters, uniforms=uniforms,
                                            seed=seed)
 
+    def probcover_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, delta=None, groups=None, alpha=0.95, fill=None,
+                          random_state=None):
+        """Extension: ProbCover queries (probcover.py; Yehuda et al. 2022) among the pairs (li[p], ri[p]) gathered from ONE left
+        and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs (indices into
+        li / ri) that are labelled already: their balls are covered before the first pick.  delta=None takes the purity radius of
+        `groups` (cluster.kmeans_device's "assign" over the same pairs).  The members are not consulted: the strategy needs no
+        scorer.  -> (picks int64 NumPy array, info), probcover.probcover_device's."""
+        from . import probcover as _probcover
+        self._one_feature_space(emb_left, emb_right)
+        return _probcover.probcover_device((emb_left, emb_right, li, ri), labelled, n_instances, delta=delta, groups=groups, alpha=alpha,
+                                           fill=fill, random_state=random_state)
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

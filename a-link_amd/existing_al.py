@@ -9,8 +9,8 @@ from .learners import ActiveLearner
 
 
 def get_strategy_object(query_strategy):
-    """code/existing_al.py:43-49; 'egl_sampling', 'badge_sampling', 'kmeans_sampling', 'diverse_minibatch_sampling' and
-    'typiclust_sampling' are this package's additions"""
+    """code/existing_al.py:43-49; 'egl_sampling', 'badge_sampling', 'kmeans_sampling', 'diverse_minibatch_sampling',
+    'typiclust_sampling' and 'probcover_sampling' are this package's additions"""
     if query_strategy == 'uncertainty_sampling':
         return uncertainty.uncertainty_sampling
     elif query_strategy == 'margin_sampling':
@@ -32,6 +32,9 @@ def get_strategy_object(query_strategy):
     elif query_strategy == 'typiclust_sampling':          # EXTENSION (typiclust.py)
         from . import typiclust
         return typiclust.typiclust_sampling
+    elif query_strategy == 'probcover_sampling':          # EXTENSION (probcover.py)
+        from . import probcover
+        return probcover.probcover_sampling
 
 
 def run_baseline(model, dataGen, query_strategy='uncertainty_sampling', active_ratio=1.0, out_model=None, verbose=1,

@@ -801,6 +801,73 @@ size_t alink_group_argmax_scratch_bytes(int64_t N, int G);
 int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t N, int G,
                        int32_t* dev_best,                  /* (G) */
                        void* dev_scratch, void* stream);
+/* EXTENSION — the fixed-radius neighbour graph of a pool and the greedy maximum coverage over it: ProbCover
+ * (Yehuda, Dekel, Hacohen & Weinshall 2022, "Active Learning Through a Covering Lens"; a-link_amd/probcover.py).  The pool as
+ * alink_knn takes it: an (N, D) row table dev_x (dev_li == NULL), or row n = |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the
+ * fly.  dev_group: (N) int32 or NULL (every row in group 0).  The rule:
+ *   eligible    a row whose group is >= 0 and whose |x|^2 (below) is finite.  A row that is not eligible has no ball, lies in
+ *               nobody's ball, is never covered and is never picked.
+ *   score       dot(n, j) = x_n . x_j — float32, ONE fused multiply-add per element from 0 in ascending element order
+ *               e = 0 .. D - 1, the chain of alink_kmeans / alink_knn (what one MFMA accumulator gives: a function of D alone, and
+ *               symmetric in (n, j) because each product is);  xn_j = |x_j|^2 — float32, the squared distance of x_j to the zero
+ *               row in alink_ranked_batch's order (alink_knn's value);  t(n, j) = fmaf(-2, dot(n, j), xn_n + xn_j): one float32
+ *               addition, which commutes, then one fused rounding — t(n, j) and t(j, n) are the same bits.
+ *   edge        j is in ball(n) when both rows are eligible and t(n, j) < radius2 — strict, as in the paper's code — or j == n: an
+ *               eligible row is always in its own ball.  The decision is symmetric: n covers j exactly when j covers n.  Groups
+ *               do not limit a ball: it holds rows of every group.  radius2 = delta^2 is a float32 the caller passes.
+ *   purity      t_other(n) = the least t(n, j) over eligible j of a DIFFERENT group than n's, by `<` from +inf: ties go to the
+ *               lower j; j_other(n) = that j, -1 (and t_other = +inf) where there is none or n is not eligible.  A ball of
+ *               radius^2 r2 round n is impure exactly when t_other(n) < r2, so ONE pass gives the whole purity curve; it does not
+ *               depend on the radius2 of the call.
+ *   graph       CSR: offsets int64 (N + 1), the exclusive prefix sum of the degrees (the caller forms it); nbr int32 (E), each
+ *               row's neighbours in ascending index order.
+ * alink_ball_count writes dev_deg (N) int32, the size of every ball (0 for a row that is not eligible), dev_t_other (N) float32 and
+ * dev_j_other (N) int32.  Each may be NULL, not all three; dev_t_other / dev_j_other need dev_group.  Two launches.
+ * alink_ball_fill makes the same pass and the same decisions bit for bit (one device function forms the score and decides the
+ * edge in both) and writes dev_nbr (E) int32: row n's neighbours at dev_offsets[n] .. dev_offsets[n + 1] - 1, ascending, every slot
+ * once, without atomics (per 32 candidates the two lanes of a row OR their decision masks; a lane writes candidate c at
+ * offsets[n] + base + popc(mask below c)).  A row never writes at or past dev_offsets[n + 1] nor outside [0, E): such a write is
+ * dropped.  dev_mismatch (1) int32 = the number of rows whose ball did not exactly fill their span — 0 whenever the offsets are
+ * the prefix sum of alink_ball_count's degrees for the same arguments; written by plain stores from a final one-workgroup launch.
+ * Three launches.  Both: dev_scratch >= alink_ball_scratch_bytes(N, D) (0 for sizes the calls refuse); where the rows are small
+ * integers nothing rounds, and everything equals a-link_amd/probcover.py: ball_graph / nearest_other (host float64) bit for bit.
+ * alink_max_coverage — greedy maximum coverage over such a graph.  dev_covered (N) uint8, in: rows covered already (nonzero),
+ * out: after the last pick.  First every row of ball(s) of every seed s in dev_seed (S, int32; NULL with S = 0; a seed outside
+ * 0 .. N - 1 is ignored) is covered — the labelled rows.  Then for t = 0 .. k - 1: degree_t(u) = the number of v in ball(u) not
+ * covered; the pick is the u of largest degree by `>` from 0, ties to the lower u; dev_picks[t] = u, dev_gain[t] = its degree;
+ * every row of ball(u) is covered.  If the largest degree is 0 the pick is -1 with gain 0, and so is every later one: an
+ * uncovered eligible row counts itself, so this means the pool is covered.  Launches: one for the seeds, two per pick — a recount
+ * (rows in contiguous chunks of 64, a wave striding a row's span of nbr, each chunk writing its (largest degree, lowest row)) and
+ * a pick (ONE workgroup combines the chunks in ascending order, writes pick and gain, marks ball(pick) with plain byte stores
+ * of 1).  Recounting streams the E edges per pick (alink_ranked_batch streams the pool per pick).  A neighbour outside
+ * 0 .. N - 1 is neither counted nor marked.  dev_scratch >= alink_max_coverage_scratch_bytes(N, k).
+ * All three calls enqueue on `stream` and return: the stream's order is the only ordering between workgroups — no cooperative
+ * launch, no grid barrier, no atomics, nothing read back, no host synchronisation; results are bit-identical from run to run;
+ * the (N x N) scores never exist in memory.  ALINK_EINVAL, nothing launched and no output touched: a NULL required argument
+ * (dev_x, dev_scratch; every output of the count; dev_offsets, dev_nbr, dev_mismatch of the fill; dev_offsets, dev_nbr,
+ * dev_covered, dev_picks, dev_gain of the greedy; dev_seed with S > 0), dev_t_other / dev_j_other without dev_group, a pair form
+ * without dev_r / dev_ri, N outside 1 .. 2^31 - 1, D outside 1 .. 8192, radius2 not finite or <= 0, E < 0, k < 1, S < 0, dev_scratch
+ * not 256-byte aligned.  Not here: distances stored with the edges, skipping tiles by a spatial bound (every workgroup walks the
+ * whole pool), an incremental-degree greedy, a cosine metric, a rectangular form (balls round a separate set of centres), several
+ * ranks' pools in one call. */
+size_t alink_ball_scratch_bytes(int64_t N, int D);
+int alink_ball_count(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                     const int32_t* dev_group, float radius2,
+                     int32_t* dev_deg,                     /* (N) or NULL */
+                     float* dev_t_other,                   /* (N) or NULL */
+                     int32_t* dev_j_other,                 /* (N) or NULL */
+                     void* dev_scratch, void* stream);
+int alink_ball_fill(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
+                    const int32_t* dev_group, float radius2, const int64_t* dev_offsets, int64_t E,
+                    int32_t* dev_nbr,                      /* (E) */
+                    int32_t* dev_mismatch,                 /* (1) */
+                    void* dev_scratch, void* stream);
+size_t alink_max_coverage_scratch_bytes(int64_t N, int k);
+int alink_max_coverage(const int64_t* dev_offsets, const int32_t* dev_nbr, int64_t N, const int32_t* dev_seed, int64_t S, int k,
+                       uint8_t* dev_covered,               /* (N) in / out */
+                       int32_t* dev_picks,                 /* (k) picks in order, -1 = the pool is covered */
+                       int32_t* dev_gain,                  /* (k) */
+                       void* dev_scratch, void* stream);
 /* Identification over a (P, G, C) score array — P probes, G gallery entries, C scores per pair — one row reduction per probe
  * (code/ALINK_MTP.py:285-287: np.argmax of the squeezed (G, 2) scores of one probe, compared with the person id).  Any of the
  * three outputs may be NULL; every result is a pure function of the row (no atomics, fixed reduction order):

@@ -195,6 +195,9 @@ PROTOTYPES = {
     "alink_knn": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, C.c_double] + [_vp] * 4 + [_vp, _vp]),
     "alink_group_argmax_scratch_bytes": (_sz, [_i64, _i]),
     "alink_group_argmax": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "alink_knn_rect_scratch_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "alink_knn_rect": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, _i] + [_vp] * 3 + [_vp, _vp]),
+    "alink_cal_score": (_i, [_vp, _vp, _i, _vp, _i64, _i64, _i, _vp, _vp]),
     "alink_ball_scratch_bytes": (_sz, [_i64, _i]),
     "alink_ball_count": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f] + [_vp] * 3 + [_vp, _vp]),
     "alink_ball_fill": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -209,6 +209,24 @@ class Bagging:
         return _probcover.probcover_device((emb_left, emb_right, li, ri), labelled, n_instances, delta=delta, groups=groups, alpha=alpha,
                                            fill=fill, random_state=random_state)
 
+    def cal_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, k_nn=10):
+        """Extension: Contrastive Active Learning queries (cal.py; Margatina et al. 2021) among the pairs (li[p], ri[p]) gathered
+        from ONE left and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs
+        (indices into li / ri, at least one) that are labelled already.  A pair's score is the mean KL divergence between the
+        committee's mean probabilities (predict_indexed) for its k_nn nearest labelled pairs and for itself; labelled pairs
+        are never picked (their scores count as -inf in the top-k).  -> (picks int32 (n,) on the device, info), cal.cal_device's."""
+        from . import cal as _cal
+        from .typiclust import _labelled_indices
+        self._one_feature_space(emb_left, emb_right)
+        probs = self.predict_indexed(emb_left, emb_right, li, ri)
+        lab = _labelled_indices(labelled, int(li.numel()))
+        if len(lab) == 0:
+            raise ValueError("cal_indexed needs at least one labelled pair: the score contrasts a pair with its labelled neighbours")
+        take = self._device_heads()[0].torch.from_numpy(lab).to(li.device)
+        references = (emb_left, emb_right, li.index_select(0, take), ri.index_select(0, take))
+        return _cal.cal_device((emb_left, emb_right, li, ri), references, probs, probs.index_select(0, take), n_instances, k_nn=k_nn,
+                               exclude=lab)
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

@@ -28,7 +28,8 @@
 //   mc_pick_kernel   per pick: ONE workgroup combines the chunks in ascending order, writes pick and gain, marks ball(pick) with
 //                    plain byte stores of 1
 // Measured: DESIGN.md §9.  Not built: distances stored with the edges, skipping tiles by a spatial bound, an incremental-degree
-// greedy, a cosine metric, a rectangular form, several ranks' pools in one call.
+// greedy, a cosine metric, balls round a separate set of centres (knn_rect.hip has the rectangular product, for lists of K, not
+// for balls), several ranks' pools in one call.
 #include "batch_rows.h"
 
 namespace alink {

@@ -27,8 +27,9 @@ small pools only); the `_device` forms are alink_ball_count, alink_ball_fill and
 on the matrix cores, never in memory; a streaming recount per pick).  On the device t is formed in float32 in an order that makes
 t(n, j) and t(j, n) the same bits; where nothing rounds, as on small-integer rows, host and device agree bit for bit.
 
-Not built: distances stored with the edges, skipping tiles by a spatial bound, an incremental-degree greedy, a cosine metric, a
-rectangular form (balls round a separate set of centres), several ranks' pools in one call.
+Not built: distances stored with the edges, skipping tiles by a spatial bound, an incremental-degree greedy, a cosine metric,
+balls round a separate set of centres (cal.knn_rect_device searches a separate set, for lists of k, not for balls), several
+ranks' pools in one call.
 """
 import numpy as np
 

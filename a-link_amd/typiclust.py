@@ -41,8 +41,8 @@ The selection rule of `typiclust` / `typiclust_device`:
 
 Deliberate difference from the public implementation: that code shrinks k to half the cluster size for small clusters; here the
 mean runs over min(k, found) neighbours — in a cluster of c rows, over its other c - 1 rows when c - 1 < k.
-Not built: a rectangular form (queries against a separate reference set), k > 32, a cosine metric, several ranks' pools in one
-call, skipping candidate tiles that hold no row of a workgroup's groups.
+Queries against a separate reference set: cal.knn_rect / cal.knn_rect_device.  Not built: k > 32, a cosine metric, several
+ranks' pools in one call, skipping candidate tiles that hold no row of a workgroup's groups.
 """
 import numpy as np
 

@@ -779,8 +779,8 @@ int alink_kmeans(const float* dev_x, const float* dev_r, const int32_t* dev_li, 
  * synchronisation, no cooperative launch, no grid barrier, no atomics, nothing read back; the (N x N) scores never exist in memory.
  * ALINK_EINVAL, nothing launched and no output touched: dev_x, dev_idx or dev_scratch NULL, a pair form without dev_r / dev_ri,
  * N outside 1 .. 2^31 - 1, D outside 1 .. 8192, K outside 1 .. 32, dev_scratch not 256-byte aligned.  dev_scratch >=
- * alink_knn_scratch_bytes(N, D, K) (0 for sizes the call refuses).  Not here: a rectangular form (queries against a separate
- * reference set), K > 32, a cosine metric, several ranks' pools in one call, skipping candidate tiles that hold no row of a
+ * alink_knn_scratch_bytes(N, D, K) (0 for sizes the call refuses).  Queries against a separate reference set: alink_knn_rect
+ * below.  Not here: K > 32, a cosine metric, several ranks' pools in one call, skipping candidate tiles that hold no row of a
  * workgroup's groups (every workgroup walks the whole pool, with or without dev_group). */
 size_t alink_knn_scratch_bytes(int64_t N, int D, int K);
 int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
@@ -801,6 +801,59 @@ size_t alink_group_argmax_scratch_bytes(int64_t N, int G);
 int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t N, int G,
                        int32_t* dev_best,                  /* (G) */
                        void* dev_scratch, void* stream);
+/* EXTENSION — the K nearest rows of a separate REFERENCE set for every QUERY row (the rectangular form of
+ * alink_knn), and the score of Contrastive Active Learning over such lists (Margatina, Vernikos, Barrault & Aletras 2021;
+ * a-link_amd/cal.py).  Queries (N rows) and references (M rows) are each given as alink_knn takes a pool: an (., D) row table
+ * (the li pointer NULL), or row n = |x[li[n]] - r[ri[n]]| formed on the fly.  ONE form holds for both sides of a call — both
+ * tables or both pair forms; in the pair form the two sides may share tables or bring their own.  A mixed call is refused: the
+ * caller can materialise the smaller side.  16-byte loads are used only when D % 4 == 0 and every table pointer of both sides is
+ * 16-byte aligned.  The rule:
+ *   score       dot(n, j) = q_n . c_j — float32, ONE fused multiply-add per element from 0 in ascending element order
+ *               e = 0 .. D - 1, the chain of alink_kmeans / alink_knn (what one MFMA accumulator gives: a function of D alone);
+ *               cn_j = |c_j|^2 — float32, the squared distance of c_j to the zero row in alink_ranked_batch's order, exactly as
+ *               alink_knn's xn_j;  score(n, j) = fmaf(-2, dot(n, j), cn_j), one rounding.
+ *   candidates  of query n: every reference — there is no self-exclusion, the sets are different, and there are no groups.  A
+ *               reference whose cn_j is NaN or +inf is nobody's neighbour; a query whose own |q_n|^2 (the same order) is NaN or
+ *               +inf has no neighbours; a score that is NaN or +inf never enters a list.
+ *   list        query n's neighbours are the K references of least (score, index) in lexicographic order, written in that order:
+ *               ties go to the lower reference index.  dev_found[n] = how many there are (<= min(K, M)); unfilled slots hold
+ *               index -1 and d2 = NaN.
+ *   distance    d2(n, slot) = |q_n - c_j|^2 for the K winners only — float32, direct differences in alink_ranked_batch's order.
+ *               The ORDER of a list is the score's, not d2's (see alink_knn).
+ * Where the rows are small integers nothing rounds, and idx, d2 and found equal a-link_amd/cal.py: knn_rect (host float64) bit
+ * for bit.  Results are bit-identical from run to run.  dev_idx (N, K) int32, indices into the references, is required; dev_d2
+ * (N, K) float32 and dev_found (N) int32 may each be NULL.  The call enqueues at most 4 launches on `stream` (the two norm passes,
+ * the list pass, the distance pass) and returns: no host synchronisation, no cooperative launch, no grid barrier, no atomics,
+ * nothing read back; the (N x M) scores never exist in memory.  A workgroup owns 128 queries and walks all M references, so
+ * ceil(N / 128) workgroups run.  ALINK_EINVAL, nothing launched and no output touched: dev_qx, dev_cx, dev_idx or dev_scratch
+ * NULL, a pair form without its r / ri, mixed forms, N or M outside 1 .. 2^31 - 1, D outside 1 .. 8192, K outside 1 .. 32,
+ * dev_scratch not 256-byte aligned.  dev_scratch >= alink_knn_rect_scratch_bytes(N, M, D, K) (0 for sizes the call refuses).
+ * Not here: splitting the references over workgroups (a handful of queries against a huge gallery), K > 32, groups, a cosine
+ * metric, several ranks' pools in one call.
+ * alink_cal_score — dev_score[n] = the mean over query n's found neighbours of KL(neighbour || query), the direction of the
+ * authors' code.  dev_p (N, C) float32, the queries' probabilities; dev_q (M, C) float32, the references'; dev_idx (N, K) as
+ * alink_knn_rect writes it.  All arithmetic is float64 from the float32 inputs, every product and sum rounded once:
+ *   p'_c  = p[n, c] if p[n, c] > 2^-126, else 2^-126
+ *   kl(j) = sum over c ascending, from 0, of q[j, c] * (log(q[j, c]) - log(p'_c)) — over the c with q[j, c] > 0 only
+ *   score = (sum over the slots ascending, from 0, of kl(idx[n, slot]) — over the slots with 0 <= idx < M only) / found,
+ * found = the number of those slots; dev_score[n] = (float)score, 0 for a query with found = 0.  The floor on p' keeps the score
+ * finite where a float32 softmax has saturated to exactly 0 (the public code works on log-softmax outputs and cannot meet one).
+ * An index >= M in dev_idx is the caller's error: such a slot is skipped like an unfilled one, the references are never read
+ * through it.  One launch, one thread per query, no atomics, nothing read back.  ALINK_EINVAL, nothing launched: a NULL pointer,
+ * N or M outside 1 .. 2^31 - 1, K outside 1 .. 32, C outside 1 .. 32. */
+size_t alink_knn_rect_scratch_bytes(int64_t N, int64_t M, int D, int K);
+int alink_knn_rect(const float* dev_qx, const float* dev_qr, const int32_t* dev_qli, const int32_t* dev_qri, int64_t N,
+                   const float* dev_cx, const float* dev_cr, const int32_t* dev_cli, const int32_t* dev_cri, int64_t M,
+                   int D, int K,
+                   int32_t* dev_idx,                       /* (N, K) indices into the references, required */
+                   float* dev_d2,                          /* (N, K) or NULL */
+                   int32_t* dev_found,                     /* (N) or NULL */
+                   void* dev_scratch, void* stream);
+int alink_cal_score(const float* dev_p,                    /* (N, C) the queries' probabilities */
+                    const float* dev_q,                    /* (M, C) the references' probabilities */
+                    int C, const int32_t* dev_idx, int64_t N, int64_t M, int K,
+                    float* dev_score,                      /* (N) */
+                    void* stream);
 /* EXTENSION — the fixed-radius neighbour graph of a pool and the greedy maximum coverage over it: ProbCover
  * (Yehuda, Dekel, Hacohen & Weinshall 2022, "Active Learning Through a Covering Lens"; a-link_amd/probcover.py).  The pool as
  * alink_knn takes it: an (N, D) row table dev_x (dev_li == NULL), or row n = |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the
@@ -848,8 +901,8 @@ int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t
  * dev_covered, dev_picks, dev_gain of the greedy; dev_seed with S > 0), dev_t_other / dev_j_other without dev_group, a pair form
  * without dev_r / dev_ri, N outside 1 .. 2^31 - 1, D outside 1 .. 8192, radius2 not finite or <= 0, E < 0, k < 1, S < 0, dev_scratch
  * not 256-byte aligned.  Not here: distances stored with the edges, skipping tiles by a spatial bound (every workgroup walks the
- * whole pool), an incremental-degree greedy, a cosine metric, a rectangular form (balls round a separate set of centres), several
- * ranks' pools in one call. */
+ * whole pool), an incremental-degree greedy, a cosine metric, balls round a separate set of centres (alink_knn_rect has the
+ * rectangular product; a ball form of it does not exist), several ranks' pools in one call. */
 size_t alink_ball_scratch_bytes(int64_t N, int D);
 int alink_ball_count(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
                      const int32_t* dev_group, float radius2,

@@ -623,11 +623,14 @@ static void r50_grad_layout(const alink_resnet50* r, int n, R50GradLayout* L) {
 // above the exponents already held.  Synchronous when != 0.  (ScaleCalibration::settle.)
 // GL != nullptr: the cached forward — the same launches, every kept output written to its own slot of the activation cache
 // instead of one of the four rotating buffers (the kernels see other addresses, nothing else: bit-identical results)
+// stop > 0: the loop ends after its first `stop` ops (alink_debug_resnet50_embed_prefix); a prefix short of the average pool
+// does not touch dev_out, which may then be NULL
 static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
                    size_t ws_bytes, hipStream_t st, float* ms, double* flops, int* n_ops, int calib = 0,
-                   const R50GradLayout* GL = nullptr) {
+                   const R50GradLayout* GL = nullptr, int stop = 0) {
     ALINK_REQUIRE(r && r->finalized, ALINK_ESTATE, "alink_resnet50_embed before finalize");
-    ALINK_REQUIRE(dev_in && dev_out && ws && n > 0, ALINK_EINVAL, "bad argument");
+    const bool need_out = stop <= 0 || stop >= (int)r->ops.size();
+    ALINK_REQUIRE(dev_in && (dev_out || !need_out) && ws && n > 0, ALINK_EINVAL, "bad argument");
     ALINK_REQUIRE(((uintptr_t)ws & 255) == 0, ALINK_EINVAL, "workspace must be 256-byte aligned");
     ALINK_REQUIRE(ws_bytes >= (GL ? GL->total : alink_resnet50_workspace_bytes(r, n)), ALINK_ENOMEM, "workspace too small");
     const bool x2 = r->dtype == ALINK_DT_F16X2;
@@ -645,6 +648,7 @@ static int r50_run(alink_resnet50_t* r, const float* dev_in, int n, int preproce
     int rc, k = 0;
     if ((rc = mark())) return rc;
     for (Op& op : r->ops) {
+        if (stop > 0 && k == stop) break;
         double fl = 0.0;
         if (GL && op.out_buf >= 0) bptr[op.out_buf] = (char*)ws + (op.slot >= 0 ? GL->slot[op.slot] : GL->scratch);
         if (op.kind == 0) {
@@ -944,6 +948,41 @@ int alink_resnet50_profile(alink_resnet50_t* r, const float* dev_in, int n_image
 
 const char* alink_resnet50_op_name(const alink_resnet50_t* r, int i) {
     return (r && i >= 0 && i < (int)r->ops.size()) ? r->ops[i].name.c_str() : "";
+}
+
+// diagnostic (include/alink_hip_debug.h): the forward stopped after its first n_ops ops, and where and what op n_ops - 1 wrote
+int alink_debug_resnet50_embed_prefix(alink_resnet50_t* r, const float* dev_in, int n, int preprocessed, float* dev_out, void* ws,
+                                      size_t ws_bytes, void* stream, int n_ops, size_t* byte_offset, int* H, int* W, int* C,
+                                      char* name_buf, int name_len, int* kernel, int* form, int* scale_exp_out) {
+    if (!r || !r->finalized) { set_error("alink_debug_resnet50_embed_prefix before finalize"); return -1; }
+    const int nops = (int)r->ops.size();
+    if (n_ops <= 0) return nops;
+    if (n_ops > nops) { set_error("the network has %d ops, asked for %d", nops, n_ops); return -1; }
+    DeviceGuard dg(r->device);
+    const bool x2 = r->dtype == ALINK_DT_F16X2;
+    const Op& op = r->ops[n_ops - 1];
+    if (n > 0) {
+        const size_t one = ((size_t)n * r->buf_elems_per_image * (x2 ? 4 : 2) + 255) & ~(size_t)255;
+        if (byte_offset) *byte_offset = op.kind == 3 ? 0 : one * op.out_buf;
+    }
+    if (H) *H = op.kind == 0 ? r->Ho1 : (op.kind == 1 ? r->Hp : (op.kind == 2 ? op.cp.Ho : 1));
+    if (W) *W = op.kind == 0 ? r->Wo1 : (op.kind == 1 ? r->Wp : (op.kind == 2 ? op.cp.Wo : 1));
+    if (C) *C = op.kind == 2 ? op.cp.Cout : (op.kind == 3 ? 2048 : 64);
+    if (name_buf && name_len > 0) snprintf(name_buf, (size_t)name_len, "%s", op.name.c_str());
+    if (kernel) *kernel = op.kind == 2 ? (int)op.kernel : -1;
+    if (form) {
+        *form = 0;
+        if (op.kind == 2 && n > 0) {
+            ConvParams p = op.cp;
+            with_batch(p, n);
+            *form = served_form(op.kernel, r->dtype, p);
+        }
+    }
+    // the exponent r50_run's bexp[] holds for this output: the op's own, the stem's behind the max-pool; the features are in true units
+    if (scale_exp_out) *scale_exp_out = !x2 || op.kind == 3 ? 0 : (op.kind == 1 ? r->ops[0].e_out : op.e_out);
+    if (r50_run(r, dev_in, n, preprocessed, dev_out, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, nullptr, 0, nullptr, n_ops))
+        return -1;
+    return nops;
 }
 
 }  // extern "C"

@@ -128,6 +128,23 @@ int alink_debug_vgg16_embed_prefix(struct alink_vgg16* r, const float* dev_in, i
                                    void* ws, size_t ws_bytes, void* stream, int n_ops, size_t* byte_offset, int* H, int* W,
                                    int* C, char* name_buf, int name_len, int* kernel, int* form);
 
+/* ---- the ResNet-50 forward stopped early (csrc/resnet50.hip) --------------------------------------------------------------- */
+/* alink_resnet50_embed's own op loop, run for ops [0, n_ops) only, on the caller's workspace: the arguments of
+ * alink_resnet50_embed, then n_ops and what op n_ops - 1 wrote.  The network is 55 ops in execution order: "conv1/7x7_s2" (the
+ * stem), "max_pool", the 52 convolutions (per unit "convS_U_1x1_reduce", "convS_U_3x3", on a stage's first unit
+ * "convS_U_1x1_proj", then "convS_U_1x1_increase") and "avg_pool"; the names are alink_resnet50_op_name's.  Reported for op
+ * n_ops - 1: the byte offset of its output from the workspace pointer, its shape [n_images][H][W][C] in the handle's 16-bit
+ * type (split precision: [n_images][H][W][2 C] halves, each 64-channel chunk [hi 64 | lo 64]), its name, the ConvKernel chosen
+ * at finalize (csrc/conv_kernel.h; -1 for the stem and the pools), the form that serves this launch (0 = that kernel,
+ * 1 = conv3x3_lat_kernel, 2 = conv_gemm_lat_kernel) and, in split precision, the exponent e of that output (stored value =
+ * true value x 2^e; 0 in the 16-bit types and for the features).  With n_ops = 55 the output is the float32 features in
+ * dev_out ([n_images][2048], H = W = 1, byte_offset 0); a shorter prefix does not touch dev_out, which may then be NULL.  Any
+ * out pointer may be NULL.  Returns the number of ops, or -1 with alink_last_error set; with n_ops <= 0 nothing is launched
+ * and nothing filled.  Tests only (tests/test_gpu_resnet50_layers.py). */
+int alink_debug_resnet50_embed_prefix(struct alink_resnet50* r, const float* dev_in, int n_images, int preprocessed, float* dev_out,
+                                      void* ws, size_t ws_bytes, void* stream, int n_ops, size_t* byte_offset, int* H, int* W,
+                                      int* C, char* name_buf, int name_len, int* kernel, int* form, int* scale_exp);
+
 #ifdef __cplusplus
 }
 #endif

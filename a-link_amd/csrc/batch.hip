@@ -42,11 +42,6 @@ __device__ __forceinline__ RbCand rb_wave_max(RbCand a) {
     }
     return a;
 }
-__device__ __forceinline__ float rb_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
 
 // alpha (1 - 1 / (1 + sqrt(d2))) + (1 - alpha) u: every operation rounded once, sqrt and division correctly rounded (the
 // compiler's default for float), no product contracted into the sum

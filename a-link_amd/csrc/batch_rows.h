@@ -74,6 +74,13 @@ __device__ __forceinline__ float rb_acc(float s, const float4& x, const float4& 
     return s;
 }
 
+// the 64 lane sums in the xor butterfly (32, 16, ..., 1): every lane ends with the same bits
+__device__ __forceinline__ float rb_wave_sum(float s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
 // s[4 a + b] = this lane's share of the distance between pool row a and labelled row b of a 4 x 4 block.  The 64 lanes' shares
 // of every distance meet in the butterfly of a plain wave sum (levels 32, 16, ..., 1: the same additions, so the same bits),
 // but packed: at each of the first four levels a lane keeps half of the sums it holds and hands the other half to its partner,

@@ -4,28 +4,26 @@
 // include/alink_hip.h (alink_kmeans) states the rule in full.
 //
 // What bounds it: the assignment is an (N x D)(D x K) product with an argmin epilogue — the selection side's first kernel on the
-// matrix cores.  v_mfma_f32_32x32x2_f32 is bit for bit an ascending fmaf chain (sgemm.hip), so x . c is ONE chain over
-// e = 0 .. D - 1 from 0 whatever tile a row or a centre falls in: the accumulator lives across the D-chunks, a tail is padded with
-// zeros (fma(0, 0, acc) = acc).  The (N x K) product never exists: a wave keeps the running (score, centre) minimum of its 32 rows
-// in registers across ALL centre tiles.
+// matrix cores, the tile product of pool_tile.h (which describes the geometry and why x . c is ONE ascending fmaf chain whatever
+// tile a row or a centre falls in).  The (N x K) product never exists: a wave keeps the running (score, centre) minimum of its
+// 32 rows in registers across ALL centre tiles.
 //
 // Launches, all on the caller's stream, whose order is the ONLY ordering between workgroups (no cooperative launch, no grid
 // barrier, no floating-point atomics, no atomics at all, nothing read back).  Per pass t = 0 .. T:
-//   km_norm_kernel    |c_j|^2 of the centres of this pass, one wave per centre, in the summation order of batch_rows.h
-//   km_assign_kernel  workgroup = 128 rows (4 waves x 32), walks the centres in tiles of 128 (4 MFMA row blocks of 32 per wave).
-//                     Both operands go through LDS in chunks of 32 columns, stored column-major so that an MFMA operand read is
-//                     conflict-free; the pair form takes |l - r| while staging.  MFMA M = centres, N = rows: lane (l, h) of a wave
-//                     holds for row l the 16 centres (r & 3) + 8 (r >> 2) + 4 h of each block — ascending in r, so a strict `<`
-//                     keeps the lower centre among ties; the two halves meet once at the end in one exchange with lane ^ 32
-//                     (ties to the lower index).  A padded centre has |c|^2 = +inf and a padded row is dropped: padding never wins.
-//                     Writes a_n into scratch.
+//   pt_norm_kernel    (pool_tile.h) over the centres as a row table: |c_j|^2 of this pass, one wave per centre, in the summation
+//                     order of batch_rows.h
+//   km_assign_kernel  pt_product per tile of 128 centres — a pair-form pool against row-table centres, each with a load width of
+//                     its own.  In a lane the 16 centres of a block come in ascending order, so a strict `<` keeps the lower
+//                     centre among ties; the two halves of a row meet once at the end in one exchange with lane ^ 32 (ties to the
+//                     lower index).  A padded centre has |c|^2 = +inf and a padded row is dropped: padding never wins.  Writes a_n
+//                     into scratch.
 //   km_dist_kernel    the light pass: d2_n = |x_n - c_(a_n)|^2 in batch_rows.h's difference form and order, `changed` against the
 //                     previous pass's dev_assign (then overwritten by the same wave: no other workgroup reads that row), and the
 //                     float64 inertia, one partial per workgroup over its contiguous chunk of rows.
 //   km_reduce_kernel  one workgroup: the partials in ascending order -> inertia[t], changed[t]
 //   km_accum_kernel   grid (K, S, ceil(D / 256)), one wave each: wave (j, s, b) scans slice s of dev_assign in ascending row order
 //                     and adds w_n x_n of cluster j's rows into float64, four columns per lane; block 0 also counts the rows, sums
-//                     the weights and keeps the slice's nearest row.  S is a function of (N, K) alone (km_slices).
+//                     the weights and keeps the slice's nearest row.  S is a function of (N, K) alone (pt_slices).
 //   km_final_kernel   one workgroup per centre: the S partials in ascending s, one float64 division, one rounding to float32 (t < T),
 //                     or counts / wsum / nearest (t = T, where km_accum_kernel runs without the column sums).
 // Hazards.  Every kernel reads only what an EARLIER launch wrote, with two exceptions that stay inside one wave: km_dist_kernel
@@ -39,27 +37,17 @@
 // scan of the assignment vector (259 us without the column sums); an iteration 0.99 / 3.19 ms.  The exact-f32 GEMM + argmin the
 // library could do before takes 1.43 / 3.53 ms for the assignment alone.
 // Not built: the early return of passes after a pass with changed = 0 (they run, and give what they must: the same again).
-#include "batch_rows.h"
+#include "pool_tile.h"
 
 namespace alink {
 namespace {
 
 constexpr int KM_MAX_K = 8192;
-constexpr int KM_TN = 128;                 // rows of a workgroup of the assignment: 32 per wave
-constexpr int KM_TK = 128;                 // centres of a tile: four MFMA row blocks per wave
-constexpr int KM_DC = 32;                  // columns of a chunk in LDS
-constexpr int KM_LD = KM_TN + 4;           // LDS row pitch (floats): column e of the tile at e * KM_LD
 constexpr int KM_MAX_GRID = 2048;          // workgroups (= partials) of the light pass
 constexpr int KM_PASS_ROWS = 2;            // rows per wave and pass of the light pass
 constexpr int KM_WG_PASS = 4 * KM_PASS_ROWS;
-constexpr int KM_SLICE_ALIGN = 256;        // rows a scanning wave takes per step
 constexpr unsigned long long KM_NO_KEY = ~0ull;
 
-__device__ __forceinline__ float km_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
 __device__ __forceinline__ double km_weight(const float* __restrict__ w, long long n) {
     if (!w) return 1.0;
     const float v = w[n];
@@ -70,99 +58,29 @@ __host__ __device__ __forceinline__ long long km_chunk_rows(long long N) {
     const long long per = (long long)KM_MAX_GRID * KM_WG_PASS;
     return KM_WG_PASS * ((N + per - 1) / per);
 }
-// slices of the update's scan: a function of (N, K) alone.  *len = rows of a slice (a multiple of 256), -> their number
-__host__ __device__ __forceinline__ int km_slices(long long N, int K, long long* len) {
-    long long S = K >= 2048 ? 1 : (4096 + K - 1) / K;
-    if (S > 64) S = 64;
-    long long L = (N + S - 1) / S;
-    L = (L + KM_SLICE_ALIGN - 1) / KM_SLICE_ALIGN * KM_SLICE_ALIGN;
-    *len = L;
-    return (int)((N + L - 1) / L);
-}
-
-// |c_j|^2: the squared distance of centre j to the zero row in the order of batch_rows.h.  One wave per centre.
-template <bool VEC>
-__global__ __launch_bounds__(256) void km_norm_kernel(const float* __restrict__ centres, int K, int D, float* __restrict__ cnorm) {
-    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (j >= K) return;
-    const RbRow c{centres + (size_t)j * D, nullptr};
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float s = 0.f;
-    for (int e0 = 4 * lane; e0 < D; e0 += 256) s = rb_acc(s, rb_quad<false, VEC>(c, e0, D), zero);
-    s = km_wave_sum(s);
-    if (lane == 0) cnorm[j] = s;
-}
-
-// columns e0 .. e0 + 3 of a tile row into the column-major tile; absent rows and columns are zeros
-template <bool PAIR, bool VEC>
-__device__ __forceinline__ float4 km_fetch(const RbRows& t, long long n, bool have, int e0) {
-    if (!have || e0 >= t.D) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return rb_quad<PAIR, VEC>(rb_row<PAIR>(t, n), e0, t.D);
-}
 
 template <bool PAIR, bool VEC, bool VECC>
 __global__ __launch_bounds__(256) void km_assign_kernel(const RbRows t, long long N, const float* __restrict__ centres,
                                                         const float* __restrict__ cnorm, int K, int32_t* __restrict__ anew) {
-    __shared__ float sX[KM_DC * KM_LD];
-    __shared__ float sC[KM_DC * KM_LD];
-    __shared__ __attribute__((aligned(16))) float sN[KM_TK];
+    __shared__ float sX[PT_DC * PT_LD];
+    __shared__ float sC[PT_DC * PT_LD];
+    __shared__ __attribute__((aligned(16))) float sN[PT_TK];
     const int D = t.D;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-    const long long n0 = (long long)blockIdx.x * KM_TN;
+    const long long n0 = (long long)blockIdx.x * PT_TN;
     const RbRows ct{centres, nullptr, nullptr, nullptr, D};
-    // staging: thread -> tile row (tid & 127), column quads (tid >> 7) + 2 q, q = 0 .. 3: a wave's lanes write 64 neighbouring
-    // floats of one LDS column at a time
-    const int srow = tid & 127, sq0 = tid >> 7;
+    const int srow = tid & 127;            // the tile row this thread stages (pool_tile.h)
     const long long xn = n0 + srow;
     const bool xhave = xn < N;
 
     float best = INFINITY;                 // a score wins by `<` alone: neither NaN nor +inf ever does
     int bestj = -1;
-    for (int k0 = 0; k0 < K; k0 += KM_TK) {
+    for (int k0 = 0; k0 < K; k0 += PT_TK) {
         const int nblk = min(4, (K - k0 + 31) >> 5);      // MFMA row blocks of this tile that hold a centre (uniform)
         const bool chave = k0 + srow < K;
         f32x16 acc[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-        for (int d0 = 0; d0 < D; d0 += KM_DC) {
-            float4 vx[4], vc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e0 = d0 + 4 * (sq0 + 2 * q);
-                vx[q] = km_fetch<PAIR, VEC>(t, xn, xhave, e0);
-                vc[q] = km_fetch<false, VECC>(ct, k0 + srow, chave, e0);
-            }
-            __syncthreads();                               // the previous chunk's operands (and the tile's norms) are read
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = 4 * (sq0 + 2 * q);
-                sX[(c + 0) * KM_LD + srow] = vx[q].x; sX[(c + 1) * KM_LD + srow] = vx[q].y;
-                sX[(c + 2) * KM_LD + srow] = vx[q].z; sX[(c + 3) * KM_LD + srow] = vx[q].w;
-                sC[(c + 0) * KM_LD + srow] = vc[q].x; sC[(c + 1) * KM_LD + srow] = vc[q].y;
-                sC[(c + 2) * KM_LD + srow] = vc[q].z; sC[(c + 3) * KM_LD + srow] = vc[q].w;
-            }
-            if (d0 == 0 && tid < KM_TK) sN[tid] = k0 + tid < K ? cnorm[k0 + tid] : INFINITY;
-            __syncthreads();
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                float xv[8], cv[4][8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * half + 2 * i + hh;
-                    xv[i] = sX[e * KM_LD + wave * 32 + l31];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) cv[b][i] = sC[e * KM_LD + b * 32 + l31];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (b < nblk) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[b][i], xv[i], acc[b], 0, 0, 0);
-                }
-            }
-        }
+        pt_product<PAIR, VEC, false, VECC>(t, xn, xhave, ct, k0 + srow, chave, nblk, sX, sC, acc,
+                                           [&](int i) { sN[i] = k0 + i < K ? cnorm[k0 + i] : INFINITY; });
         // the tile's scores against the running minimum: in a lane the centres come in ascending order
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -214,7 +132,7 @@ __global__ __launch_bounds__(256) void km_dist_kernel(const RbRows t, long long 
                 const RbRow c{centres + (size_t)a * D, nullptr};
                 float s = 0.f;
                 for (int e0 = 4 * lane; e0 < D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, D), rb_quad<false, VECC>(c, e0, D));
-                d = km_wave_sum(s);
+                d = rb_wave_sum(s);
                 const double w = km_weight(weight, n);
                 if (w > 0.0) isum += w * (double)d;
             }
@@ -271,7 +189,7 @@ __global__ __launch_bounds__(64) void km_accum_kernel(const RbRows t, long long 
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, wsum = 0.0;
     int count = 0;
     unsigned long long key = KM_NO_KEY;
-    for (long long base = r0; base < r1; base += KM_SLICE_ALIGN) {
+    for (long long base = r0; base < r1; base += PT_SLICE_ALIGN) {
         unsigned long long m[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -349,8 +267,6 @@ __global__ __launch_bounds__(256) void km_final_kernel(int D, int S, int last, c
     }
 }
 
-size_t km_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct KmScratch {
     int32_t* anew;
     float* d2;
@@ -365,10 +281,10 @@ struct KmScratch {
 };
 KmScratch km_carve(char* base, long long N, int D, int K) {
     long long slice;
-    const size_t S = (size_t)km_slices(N, K, &slice);
+    const size_t S = (size_t)pt_slices(N, K, &slice);
     KmScratch s;
     size_t o = 0;
-    auto take = [&](size_t b) { char* p = base + o; o += km_align(b); return p; };
+    auto take = [&](size_t b) { char* p = base + o; o += pt_align(b); return p; };
     s.anew = (int32_t*)take((size_t)N * 4);
     s.d2 = (float*)take((size_t)N * 4);
     s.cnorm = (float*)take((size_t)K * 4);
@@ -401,14 +317,15 @@ void km_enqueue(const RbRows& t, long long N, const KmArgs& a, char* scratch, hi
     const KmScratch s = km_carve(scratch, N, D, K);
     float* d2 = a.d2 ? a.d2 : s.d2;
     long long slice;
-    const int S = km_slices(N, K, &slice);
+    const int S = pt_slices(N, K, &slice);
     const long long chunk = km_chunk_rows(N);
     const unsigned dgrid = (unsigned)((N + chunk - 1) / chunk);            // <= KM_MAX_GRID
-    const unsigned agrid = (unsigned)((N + KM_TN - 1) / KM_TN);
+    const unsigned agrid = (unsigned)((N + PT_TN - 1) / PT_TN);
     const bool stats = a.counts || a.wsum || a.nearest;
+    const RbRows ct{a.centres, nullptr, nullptr, nullptr, D};             // the centres as a row table
     for (int pass = 0; pass <= a.iters; ++pass) {
         const bool last = pass == a.iters;
-        hipLaunchKernelGGL((km_norm_kernel<VECC>), dim3((K + 3) / 4), dim3(256), 0, st, a.centres, K, D, s.cnorm);
+        hipLaunchKernelGGL((pt_norm_kernel<false, VECC>), dim3((K + 3) / 4), dim3(256), 0, st, ct, (long long)K, s.cnorm);
         hipLaunchKernelGGL((km_assign_kernel<PAIR, VEC, VECC>), dim3(agrid), dim3(256), 0, st, t, N, a.centres, s.cnorm, K, s.anew);
         hipLaunchKernelGGL((km_dist_kernel<PAIR, VEC, VECC>), dim3(dgrid), dim3(256), 0, st, t, N, chunk, a.centres, a.weight, s.anew,
                            a.assign, d2, pass == 0 ? 1 : 0, s.part_inertia, s.part_changed);
@@ -450,7 +367,7 @@ int alink_kmeans(const float* dev_x, const float* dev_r, const int32_t* dev_li, 
     const KmArgs a{dev_weight, dev_centres, K, iters, dev_assign, dev_d2, dev_inertia, dev_changed, dev_counts, dev_wsum, dev_nearest};
     hipStream_t st = (hipStream_t)stream;
     const bool pair = dev_li != nullptr;
-    const bool vec = D % 4 == 0 && (((uintptr_t)dev_x | (pair ? (uintptr_t)dev_r : 0)) & 15) == 0;
+    const bool vec = pt_vec(t);
     const bool vecc = D % 4 == 0 && ((uintptr_t)dev_centres & 15) == 0;
     char* sc = (char*)dev_scratch;
 #define KM_GO(P, V, C) km_enqueue<P, V, C>(t, N, a, sc, st)

@@ -62,11 +62,6 @@ __device__ __forceinline__ KpCand kp_wave_max(KpCand a) {
     }
     return a;
 }
-__device__ __forceinline__ float kp_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
 // inclusive scan over the wave's 64 lanes, lane order ascending (Hillis-Steele: distances 1, 2, ..., 32)
 __device__ __forceinline__ double kp_wave_scan(double x, int lane) {
 #pragma unroll
@@ -223,7 +218,7 @@ __global__ __launch_bounds__(256) void kp_norm_kernel(const RbRows t, long long 
         }
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
-            const float sj = kp_wave_sum(s[j]);
+            const float sj = rb_wave_sum(s[j]);
             if (n0 + j < r1) best = kp_better(best, KpCand{sj, (int)(n0 + j)});
         }
     }
@@ -284,7 +279,7 @@ __global__ __launch_bounds__(256) void kp_step_kernel(const RbRows t, long long 
             }
 #pragma unroll
             for (int j = 0; j < NR; ++j) {
-                const float sj = kp_wave_sum(s[j]);
+                const float sj = rb_wave_sum(s[j]);
                 d[j] = step > 0 ? fminf(d[j], sj) : sj;
             }
         }

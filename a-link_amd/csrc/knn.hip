@@ -3,39 +3,35 @@
 // argmax that turns typicalities into queries (a-link_amd/typiclust.py).  include/alink_hip.h (alink_knn, alink_group_argmax)
 // states the rule in full.
 //
-// What bounds it: an (N x D)(D x N) product on the f32 matrix cores whose scores never reach memory — km_assign_kernel
-// (kmeans.hip) with the pool as its own centres and a running sorted list of K in place of a running minimum.
-// v_mfma_f32_32x32x2_f32 is bit for bit an ascending fmaf chain, so x_n . x_j is ONE chain over e = 0 .. D - 1 from 0 whatever tile
-// either row falls in.
+// What bounds it: an (N x D)(D x N) product on the f32 matrix cores whose scores never reach memory — the tile product of
+// pool_tile.h (which describes the geometry and why x_n . x_j is ONE ascending fmaf chain whatever tile either row falls in) with
+// the pool as its own candidates, and a running sorted list of K where kmeans.hip keeps a running minimum.
 //
 // Launches of alink_knn, all on the caller's stream, whose order is the ONLY ordering between workgroups (no cooperative launch,
 // no grid barrier, no atomics, nothing read back):
-//   kn_norm_kernel  |x_j|^2 of every row, one wave per row, in the summation order of batch_rows.h
-//   kn_list_kernel  workgroup = 128 rows (4 waves x 32), walks the pool in tiles of 128 candidates (4 MFMA row blocks of 32 per
-//                   wave).  Both operands go through LDS in chunks of 32 columns, stored column-major; the pair form takes |l - r|
-//                   while staging; the tile's norms and groups lie beside them.  MFMA M = candidates, N = rows: lane (l, h) of a
-//                   wave holds for row l the 16 candidates (r & 3) + 8 (r >> 2) + 4 h of each block — ascending in r, so a strict
-//                   `<` keeps the lower candidate among ties.  The lane's running KK best are a sorted list of (score, index) in
-//                   registers (KK = 8 / 16 / 32 at compile time, every index a constant: a smaller K is the head of the next larger
-//                   list); a candidate enters through an unrolled compare-and-shift chain, which only those candidates walk that
-//                   SOME lane of the wave holds below its KK-th — a wave-uniform vote per candidate, gathered into a 16-bit mask per
-//                   MFMA block and worked off in ascending order, so the chain stands four times in the code, not 64.  At the end
-//                   the two lanes of a row exchange their lists with lane ^ 32 and merge them on (score, index): min(A[i],
-//                   B[KK - 1 - i]) is a bitonic sequence of the KK least, log2(KK) half-cleaner stages sort it.
+//   pt_norm_kernel  (pool_tile.h) |x_j|^2 of every row, one wave per row, in the summation order of batch_rows.h
+//   kn_list_kernel  pt_product per tile of 128 candidates, the tile's norms and groups staged beside the operands.  In a lane the
+//                   16 candidates of a block come in ascending order, so a strict `<` keeps the lower candidate among ties.  The
+//                   lane's running KK best are a sorted list of (score, index) in registers (KK = 8 / 16 / 32 at compile time,
+//                   every index a constant: a smaller K is the head of the next larger list); a candidate enters through an
+//                   unrolled compare-and-shift chain, which only those candidates walk that SOME lane of the wave holds below its
+//                   KK-th — a wave-uniform vote per candidate, gathered into a 16-bit mask per MFMA block and worked off in
+//                   ascending order, so the chain stands four times in the code, not 64.  At the end the two lanes of a row
+//                   exchange their lists with lane ^ 32 and merge them on (score, index): min(A[i], B[KK - 1 - i]) is a bitonic
+//                   sequence of the KK least, log2(KK) half-cleaner stages sort it.
 //   kn_dist_kernel  the light pass, one wave per row: d2 of the K winners by direct differences in batch_rows.h's order, and the
 //                   float64 mean of the typicality in ascending slot order.
 // alink_group_argmax is two launches in the shape of km_accum_kernel / km_final_kernel: wave (g, s) scans slice s of the group
 // vector in ascending row order, then one thread per group combines the slices in ascending order.
 // Measured: DESIGN.md §9.  Not built: skipping candidate tiles that hold no row of the workgroup's groups, K > 32, a cosine
-// metric, several ranks' pools in one call.  (Queries against a separate reference set: knn_rect.hip, which shares the norm pass
-// and the list helpers of knn_lists.h with this file.)
+// metric, several ranks' pools in one call.  (Queries against a separate reference set: knn_rect.hip, which shares the list
+// helpers of knn_lists.h with this file.)
 #include "knn_lists.h"
 
 namespace alink {
 namespace {
 
 constexpr int KN_MAX_G = 8192;
-constexpr int KN_SLICE_ALIGN = 256;
 
 // Two waves per SIMD, as the assignment kernel has: asked for, because left alone the compiler spends 255 + 80 registers at
 // KK = 32 and fits one.  The one form that does not fit 256 registers without scratch — KK = 32 on a row table read with scalar
@@ -44,15 +40,13 @@ template <int KK, bool PAIR, bool VEC>
 __global__ __launch_bounds__(256, (KK == 32 && !PAIR && !VEC) ? 1 : 2) void kn_list_kernel(const RbRows t, long long N, const float* __restrict__ xnorm,
                                                       const int32_t* __restrict__ group, int K, int32_t* __restrict__ idx,
                                                       int32_t* __restrict__ found) {
-    __shared__ float sX[KN_DC * KN_LD];
-    __shared__ float sC[KN_DC * KN_LD];
-    __shared__ __attribute__((aligned(16))) float sN[KN_TK];
-    __shared__ __attribute__((aligned(16))) int sG[KN_TK];
-    const int D = t.D;
+    __shared__ float sX[PT_DC * PT_LD];
+    __shared__ float sC[PT_DC * PT_LD];
+    __shared__ __attribute__((aligned(16))) float sN[PT_TK];
+    __shared__ __attribute__((aligned(16))) int sG[PT_TK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-    const long long n0 = (long long)blockIdx.x * KN_TN;
-    // staging: thread -> tile row (tid & 127), column quads (tid >> 7) + 2 q, q = 0 .. 3
-    const int srow = tid & 127, sq0 = tid >> 7;
+    const long long n0 = (long long)blockIdx.x * PT_TN;
+    const int srow = tid & 127;            // the tile row this thread stages (pool_tile.h)
     const long long xn = n0 + srow;
     const bool xhave = xn < N;
 
@@ -71,58 +65,18 @@ __global__ __launch_bounds__(256, (KK == 32 && !PAIR && !VEC) ? 1 : 2) void kn_l
 #pragma unroll
     for (int p = 0; p < KK; ++p) { ls[p] = INFINITY; lj[p] = -1; }
 
-    for (long long k0 = 0; k0 < N; k0 += KN_TK) {
+    for (long long k0 = 0; k0 < N; k0 += PT_TK) {
         const long long left = N - k0;
-        const int nblk = left >= KN_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
+        const int nblk = left >= PT_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
         const long long cn_ = k0 + srow;
         const bool chave = cn_ < N;
         f32x16 acc[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-        for (int d0 = 0; d0 < D; d0 += KN_DC) {
-            float4 vx[4], vc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e0 = d0 + 4 * (sq0 + 2 * q);
-                vx[q] = kn_fetch<PAIR, VEC>(t, xn, xhave, e0);
-                vc[q] = kn_fetch<PAIR, VEC>(t, cn_, chave, e0);
-            }
-            __syncthreads();                               // the previous chunk's operands (and the tile's norms, groups) are read
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = 4 * (sq0 + 2 * q);
-                sX[(c + 0) * KN_LD + srow] = vx[q].x; sX[(c + 1) * KN_LD + srow] = vx[q].y;
-                sX[(c + 2) * KN_LD + srow] = vx[q].z; sX[(c + 3) * KN_LD + srow] = vx[q].w;
-                sC[(c + 0) * KN_LD + srow] = vc[q].x; sC[(c + 1) * KN_LD + srow] = vc[q].y;
-                sC[(c + 2) * KN_LD + srow] = vc[q].z; sC[(c + 3) * KN_LD + srow] = vc[q].w;
-            }
-            if (d0 == 0 && tid < KN_TK) {
-                const long long j = k0 + tid;
-                sN[tid] = j < N ? xnorm[j] : INFINITY;     // a padded candidate never enters
-                const int gj = j < N ? (group ? group[j] : 0) : -1;
-                sG[tid] = gj < 0 ? -1 : gj;                // every group < 0 is -1 here: nobody's neighbour
-            }
-            __syncthreads();
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                float xv[8], cv[4][8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * half + 2 * i + hh;
-                    xv[i] = sX[e * KN_LD + wave * 32 + l31];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) cv[b][i] = sC[e * KN_LD + b * 32 + l31];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (b < nblk) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[b][i], xv[i], acc[b], 0, 0, 0);
-                }
-            }
-        }
+        pt_product<PAIR, VEC, PAIR, VEC>(t, xn, xhave, t, cn_, chave, nblk, sX, sC, acc, [&](int i) {
+            const long long j = k0 + i;
+            sN[i] = j < N ? xnorm[j] : INFINITY;           // a padded candidate never enters
+            const int gj = j < N ? (group ? group[j] : 0) : -1;
+            sG[i] = gj < 0 ? -1 : gj;                      // every group < 0 is -1 here: nobody's neighbour
+        });
         // the tile's scores against the running list: in a lane the candidates come in ascending order
         const int jbase = (int)(unsigned)k0 + 4 * hh;
 #pragma unroll
@@ -186,23 +140,13 @@ __global__ __launch_bounds__(256) void kn_dist_kernel(const RbRows t, long long 
             const RbRow c = rb_row<PAIR>(t, j);
             float s = 0.f;
             for (int e0 = 4 * lane; e0 < D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, D), rb_quad<PAIR, VEC>(c, e0, D));
-            d = kn_wave_sum(s);
+            d = rb_wave_sum(s);
             sum += squared ? (double)d : sqrt((double)d);
             ++f;
         }
         if (lane == 0 && d2) d2[(size_t)n * K + p] = d;
     }
     if (lane == 0 && typicality) typicality[n] = f ? (float)(1.0 / (sum / (double)f + eps)) : 0.f;
-}
-
-// slices of the group scan: a function of (N, G) alone (the rule of the k-means update).  *len = rows of a slice -> their number
-__host__ __device__ __forceinline__ int ga_slices(long long N, int G, long long* len) {
-    long long S = G >= 2048 ? 1 : (4096 + G - 1) / G;
-    if (S > 64) S = 64;
-    long long L = (N + S - 1) / S;
-    L = (L + KN_SLICE_ALIGN - 1) / KN_SLICE_ALIGN * KN_SLICE_ALIGN;
-    *len = L;
-    return (int)((N + L - 1) / L);
 }
 
 // wave (g, s): the rows of group g in slice s, ascending; the largest value by `>` from -inf, ties to the lower row
@@ -256,8 +200,8 @@ struct KnArgs {
 template <bool PAIR, bool VEC>
 void kn_enqueue(const RbRows& t, long long N, const KnArgs& a, float* xnorm, hipStream_t st) {
     const unsigned wgrid = (unsigned)((N + 3) / 4);
-    const unsigned lgrid = (unsigned)((N + KN_TN - 1) / KN_TN);
-    hipLaunchKernelGGL((kn_norm_kernel<PAIR, VEC>), dim3(wgrid), dim3(256), 0, st, t, N, xnorm);
+    const unsigned lgrid = (unsigned)((N + PT_TN - 1) / PT_TN);
+    hipLaunchKernelGGL((pt_norm_kernel<PAIR, VEC>), dim3(wgrid), dim3(256), 0, st, t, N, xnorm);
     if (a.K <= 8)
         hipLaunchKernelGGL((kn_list_kernel<8, PAIR, VEC>), dim3(lgrid), dim3(256), 0, st, t, N, xnorm, a.group, a.K, a.idx, a.found);
     else if (a.K <= 16)
@@ -278,7 +222,7 @@ extern "C" {
 
 size_t alink_knn_scratch_bytes(int64_t N, int D, int K) {
     if (N <= 0 || N >= (1ll << 31) || D <= 0 || D > RB_MAX_D || K <= 0 || K > KN_MAX_K) return 0;
-    return kn_align((size_t)N * 4);
+    return pt_align((size_t)N * 4);
 }
 
 int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
@@ -295,7 +239,7 @@ int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, con
     const KnArgs a{dev_group, K, squared ? 1 : 0, eps, dev_idx, dev_d2, dev_found, dev_typicality};
     hipStream_t st = (hipStream_t)stream;
     const bool pair = dev_li != nullptr;
-    const bool vec = D % 4 == 0 && (((uintptr_t)dev_x | (pair ? (uintptr_t)dev_r : 0)) & 15) == 0;
+    const bool vec = pt_vec(t);
     float* xnorm = (float*)dev_scratch;
     if (pair) { if (vec) kn_enqueue<true, true>(t, N, a, xnorm, st); else kn_enqueue<true, false>(t, N, a, xnorm, st); }
     else { if (vec) kn_enqueue<false, true>(t, N, a, xnorm, st); else kn_enqueue<false, false>(t, N, a, xnorm, st); }
@@ -306,8 +250,8 @@ int alink_knn(const float* dev_x, const float* dev_r, const int32_t* dev_li, con
 size_t alink_group_argmax_scratch_bytes(int64_t N, int G) {
     if (N <= 0 || N >= (1ll << 31) || G <= 0 || G > KN_MAX_G) return 0;
     long long slice;
-    const size_t S = (size_t)ga_slices(N, G, &slice);
-    return kn_align((size_t)G * S * 4) * 2;
+    const size_t S = (size_t)pt_slices(N, G, &slice);
+    return pt_align((size_t)G * S * 4) * 2;
 }
 
 int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t N, int G, int32_t* dev_best, void* dev_scratch,
@@ -318,9 +262,9 @@ int alink_group_argmax(const float* dev_value, const int32_t* dev_group, int64_t
     ALINK_REQUIRE(((uintptr_t)dev_scratch & 255) == 0, ALINK_EINVAL, "scratch must be 256-byte aligned");
     DeviceGuard dg(device_of_pointer(dev_value));
     long long slice;
-    const int S = ga_slices(N, G, &slice);
+    const int S = pt_slices(N, G, &slice);
     float* pval = (float*)dev_scratch;
-    int32_t* prow = (int32_t*)((char*)dev_scratch + kn_align((size_t)G * S * 4));
+    int32_t* prow = (int32_t*)((char*)dev_scratch + pt_align((size_t)G * S * 4));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(ga_scan_kernel, dim3(G, S), dim3(64), 0, st, dev_value, dev_group, (long long)N, slice, S, pval, prow);
     hipLaunchKernelGGL(ga_final_kernel, dim3((G + 255) / 256), dim3(256), 0, st, G, S, pval, prow, dev_best);

@@ -1,45 +1,14 @@
-// knn_lists.h — what knn.hip (a pool against itself) and knn_rect.hip (queries against a separate reference set) share: the tile
-// sizes of the list kernels, the norm pass, the staging fetch, and a lane's running sorted list of (score, index) in registers —
-// insertion, the select tree that reads one of 16 registers, the (score, index) order and the merge of a row's two lanes.  The
-// header comment of knn.hip describes the kernel these serve.
+// knn_lists.h — what knn.hip (a pool against itself) and knn_rect.hip (queries against a separate reference set) share beyond the
+// tile product of pool_tile.h: a lane's running sorted list of (score, index) in registers — insertion, the select tree that reads
+// one of 16 registers, the (score, index) order and the merge of a row's two lanes.  The header comment of knn.hip describes the
+// kernel these serve.
 #pragma once
-#include "batch_rows.h"
+#include "pool_tile.h"
 
 namespace alink {
 namespace {
 
 constexpr int KN_MAX_K = 32;
-constexpr int KN_TN = 128;                 // rows of a workgroup: 32 per wave
-constexpr int KN_TK = 128;                 // candidates of a tile: four MFMA row blocks per wave
-constexpr int KN_DC = 32;                  // columns of a chunk in LDS
-constexpr int KN_LD = KN_TN + 4;           // LDS row pitch (floats): column e of the tile at e * KN_LD
-
-__device__ __forceinline__ float kn_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
-
-// |x_n|^2: the squared distance of row n to the zero row in the order of batch_rows.h.  One wave per row.
-template <bool PAIR, bool VEC>
-__global__ __launch_bounds__(256) void kn_norm_kernel(const RbRows t, long long N, float* __restrict__ xnorm) {
-    const int lane = threadIdx.x & 63;
-    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const RbRow r = rb_row<PAIR>(t, n);
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float s = 0.f;
-    for (int e0 = 4 * lane; e0 < t.D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, t.D), zero);
-    s = kn_wave_sum(s);
-    if (lane == 0) xnorm[n] = s;
-}
-
-// columns e0 .. e0 + 3 of a tile row; absent rows and columns are zeros
-template <bool PAIR, bool VEC>
-__device__ __forceinline__ float4 kn_fetch(const RbRows& t, long long n, bool have, int e0) {
-    if (!have || e0 >= t.D) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return rb_quad<PAIR, VEC>(rb_row<PAIR>(t, n), e0, t.D);
-}
 
 // a candidate of a lane's own stream (ascending index) into its sorted list: strict `<`, so it lands behind its equals
 template <int KK>
@@ -97,8 +66,6 @@ __device__ __forceinline__ void kn_merge_halves(float (&ls)[KK], int (&lj)[KK]) 
         }
     }
 }
-
-size_t kn_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace alink

@@ -4,18 +4,16 @@
 // both rules in full.
 //
 // What bounds it: an (N x D)(D x M) product on the f32 matrix cores whose scores never reach memory — kn_list_kernel (knn.hip)
-// with a second operand.  The queries are the MFMA's N side, the references walk past as its M side; v_mfma_f32_32x32x2_f32 is
-// bit for bit an ascending fmaf chain, so q_n . c_j is ONE chain over e = 0 .. D - 1 from 0 whatever tile either row falls in.
+// with a second operand.  The queries are the rows of pool_tile.h's tile product, the references walk past as its candidates.
 //
 // Launches of alink_knn_rect, all on the caller's stream, whose order is the ONLY ordering between workgroups (no cooperative
 // launch, no grid barrier, no atomics, nothing read back):
-//   kn_norm_kernel  (knn_lists.h) twice: |q_n|^2 of every query and |c_j|^2 of every reference, one wave per row
-//   kr_list_kernel  kn_list_kernel's shape (its header comment describes it): workgroup = 128 queries (4 waves x 32), walks the
-//                   references in tiles of 128 (4 MFMA row blocks of 32 per wave); both operands through LDS in chunks of 32
-//                   columns, column-major, |l - r| taken while staging; a lane's running KK best (8 / 16 / 32) a sorted list in
-//                   registers, entered through the wave vote and the unrolled compare-and-shift chain; the two lanes of a row
-//                   merge at the end.  What differs: the candidate operand and its norms come from the reference set, and there
-//                   is neither a group nor a self test — a query whose own norm is NaN or +inf holds +inf for every score.
+//   pt_norm_kernel  (pool_tile.h) twice: |q_n|^2 of every query and |c_j|^2 of every reference, one wave per row
+//   kr_list_kernel  kn_list_kernel's lists over pt_product (the header comments of knn.hip and pool_tile.h describe both): a
+//                   lane's running KK best (8 / 16 / 32) a sorted list in registers, entered through the wave vote and the
+//                   unrolled compare-and-shift chain; the two lanes of a row merge at the end.  What differs: the candidate
+//                   operand and its norms come from the reference set, and there is neither a group nor a self test — a query
+//                   whose own norm is NaN or +inf holds +inf for every score.
 //   kr_dist_kernel  the light pass, one wave per query: d2 of the K winners by direct differences in batch_rows.h's order
 // alink_cal_score is one launch, one thread per query: float64 throughout, slots and classes in ascending order.
 // Measured: DESIGN.md §9.  Not built: splitting the references over workgroups (a handful of queries against a huge gallery keeps
@@ -33,14 +31,12 @@ template <int KK, bool PAIR, bool VEC>
 __global__ __launch_bounds__(256, (KK == 32 && !PAIR && !VEC) ? 1 : 2) void kr_list_kernel(const RbRows tq, long long N, const RbRows tc, long long M,
                                                       const float* __restrict__ qnorm, const float* __restrict__ cnorm, int K,
                                                       int32_t* __restrict__ idx, int32_t* __restrict__ found) {
-    __shared__ float sX[KN_DC * KN_LD];
-    __shared__ float sC[KN_DC * KN_LD];
-    __shared__ __attribute__((aligned(16))) float sN[KN_TK];
-    const int D = tq.D;
+    __shared__ float sX[PT_DC * PT_LD];
+    __shared__ float sC[PT_DC * PT_LD];
+    __shared__ __attribute__((aligned(16))) float sN[PT_TK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-    const long long n0 = (long long)blockIdx.x * KN_TN;
-    // staging: thread -> tile row (tid & 127), column quads (tid >> 7) + 2 q, q = 0 .. 3
-    const int srow = tid & 127, sq0 = tid >> 7;
+    const long long n0 = (long long)blockIdx.x * PT_TN;
+    const int srow = tid & 127;            // the tile row this thread stages (pool_tile.h)
     const long long xn = n0 + srow;
     const bool xhave = xn < N;
 
@@ -53,56 +49,16 @@ __global__ __launch_bounds__(256, (KK == 32 && !PAIR && !VEC) ? 1 : 2) void kr_l
 #pragma unroll
     for (int p = 0; p < KK; ++p) { ls[p] = INFINITY; lj[p] = -1; }
 
-    for (long long k0 = 0; k0 < M; k0 += KN_TK) {
+    for (long long k0 = 0; k0 < M; k0 += PT_TK) {
         const long long left = M - k0;
-        const int nblk = left >= KN_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
+        const int nblk = left >= PT_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
         const long long cn_ = k0 + srow;
         const bool chave = cn_ < M;
         f32x16 acc[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-        for (int d0 = 0; d0 < D; d0 += KN_DC) {
-            float4 vx[4], vc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e0 = d0 + 4 * (sq0 + 2 * q);
-                vx[q] = kn_fetch<PAIR, VEC>(tq, xn, xhave, e0);
-                vc[q] = kn_fetch<PAIR, VEC>(tc, cn_, chave, e0);
-            }
-            __syncthreads();                               // the previous chunk's operands (and the tile's norms) are read
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = 4 * (sq0 + 2 * q);
-                sX[(c + 0) * KN_LD + srow] = vx[q].x; sX[(c + 1) * KN_LD + srow] = vx[q].y;
-                sX[(c + 2) * KN_LD + srow] = vx[q].z; sX[(c + 3) * KN_LD + srow] = vx[q].w;
-                sC[(c + 0) * KN_LD + srow] = vc[q].x; sC[(c + 1) * KN_LD + srow] = vc[q].y;
-                sC[(c + 2) * KN_LD + srow] = vc[q].z; sC[(c + 3) * KN_LD + srow] = vc[q].w;
-            }
-            if (d0 == 0 && tid < KN_TK) {
-                const long long j = k0 + tid;
-                sN[tid] = j < M ? cnorm[j] : INFINITY;     // a padded reference never enters
-            }
-            __syncthreads();
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                float xv[8], cv[4][8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * half + 2 * i + hh;
-                    xv[i] = sX[e * KN_LD + wave * 32 + l31];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) cv[b][i] = sC[e * KN_LD + b * 32 + l31];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (b < nblk) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[b][i], xv[i], acc[b], 0, 0, 0);
-                }
-            }
-        }
+        pt_product<PAIR, VEC, PAIR, VEC>(tq, xn, xhave, tc, cn_, chave, nblk, sX, sC, acc, [&](int i) {
+            const long long j = k0 + i;
+            sN[i] = j < M ? cnorm[j] : INFINITY;           // a padded reference never enters
+        });
         // the tile's scores against the running list: in a lane the references come in ascending order
         const int jbase = (int)(unsigned)k0 + 4 * hh;
 #pragma unroll
@@ -159,7 +115,7 @@ __global__ __launch_bounds__(256) void kr_dist_kernel(const RbRows tq, long long
             const RbRow c = rb_row<PAIR>(tc, j);
             float s = 0.f;
             for (int e0 = 4 * lane; e0 < D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, D), rb_quad<PAIR, VEC>(c, e0, D));
-            d = kn_wave_sum(s);
+            d = rb_wave_sum(s);
         }
         if (lane == 0) d2[(size_t)n * K + p] = d;
     }
@@ -201,9 +157,9 @@ struct KrArgs {
 template <bool PAIR, bool VEC>
 void kr_enqueue(const RbRows& tq, long long N, const RbRows& tc, long long M, const KrArgs& a, float* qnorm, float* cnorm, hipStream_t st) {
     const unsigned qgrid = (unsigned)((N + 3) / 4), cgrid = (unsigned)((M + 3) / 4);
-    const unsigned lgrid = (unsigned)((N + KN_TN - 1) / KN_TN);
-    hipLaunchKernelGGL((kn_norm_kernel<PAIR, VEC>), dim3(qgrid), dim3(256), 0, st, tq, N, qnorm);
-    hipLaunchKernelGGL((kn_norm_kernel<PAIR, VEC>), dim3(cgrid), dim3(256), 0, st, tc, M, cnorm);
+    const unsigned lgrid = (unsigned)((N + PT_TN - 1) / PT_TN);
+    hipLaunchKernelGGL((pt_norm_kernel<PAIR, VEC>), dim3(qgrid), dim3(256), 0, st, tq, N, qnorm);
+    hipLaunchKernelGGL((pt_norm_kernel<PAIR, VEC>), dim3(cgrid), dim3(256), 0, st, tc, M, cnorm);
     if (a.K <= 8)
         hipLaunchKernelGGL((kr_list_kernel<8, PAIR, VEC>), dim3(lgrid), dim3(256), 0, st, tq, N, tc, M, qnorm, cnorm, a.K, a.idx, a.found);
     else if (a.K <= 16)
@@ -226,7 +182,7 @@ extern "C" {
 
 size_t alink_knn_rect_scratch_bytes(int64_t N, int64_t M, int D, int K) {
     if (!kr_sizes_ok(N, M, D, K)) return 0;
-    return kn_align((size_t)N * 4) + kn_align((size_t)M * 4);
+    return pt_align((size_t)N * 4) + pt_align((size_t)M * 4);
 }
 
 int alink_knn_rect(const float* dev_qx, const float* dev_qr, const int32_t* dev_qli, const int32_t* dev_qri, int64_t N,
@@ -247,9 +203,9 @@ int alink_knn_rect(const float* dev_qx, const float* dev_qr, const int32_t* dev_
     const KrArgs a{K, dev_idx, dev_d2, dev_found};
     hipStream_t st = (hipStream_t)stream;
     const bool pair = dev_qli != nullptr;
-    const bool vec = D % 4 == 0 && (((uintptr_t)dev_qx | (uintptr_t)dev_cx | (pair ? (uintptr_t)dev_qr | (uintptr_t)dev_cr : 0)) & 15) == 0;
+    const bool vec = pt_vec(tq) && pt_vec(tc);
     float* qnorm = (float*)dev_scratch;
-    float* cnorm = (float*)((char*)dev_scratch + kn_align((size_t)N * 4));
+    float* cnorm = (float*)((char*)dev_scratch + pt_align((size_t)N * 4));
     if (pair) { if (vec) kr_enqueue<true, true>(tq, N, tc, M, a, qnorm, cnorm, st); else kr_enqueue<true, false>(tq, N, tc, M, a, qnorm, cnorm, st); }
     else { if (vec) kr_enqueue<false, true>(tq, N, tc, M, a, qnorm, cnorm, st); else kr_enqueue<false, false>(tq, N, tc, M, a, qnorm, cnorm, st); }
     ALINK_HIP(hipGetLastError());

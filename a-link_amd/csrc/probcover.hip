@@ -3,19 +3,18 @@
 // Weinshall 2022, "Active Learning Through a Covering Lens"; a-link_amd/probcover.py).  include/alink_hip.h (alink_ball_count,
 // alink_ball_fill, alink_max_coverage) states the rule in full.
 //
-// What bounds the graph: the (N x D)(D x N) product of knn.hip on the f32 matrix cores, whose scores never reach memory, with a
-// threshold in place of the running lists.  v_mfma_f32_32x32x2_f32 is bit for bit an ascending fmaf chain, so x_n . x_j is ONE
-// chain over e = 0 .. D - 1 from 0 whatever tile either row falls in, the same bits for (n, j) and (j, n); the two norms meet in
-// one float32 addition, which commutes: t(n, j) and t(j, n) are the same bits and the graph is symmetric.
+// What bounds the graph: the (N x D)(D x N) product of knn.hip on the f32 matrix cores — the tile product of pool_tile.h — whose
+// scores never reach memory, with a threshold in place of the running lists.  x_n . x_j is ONE ascending fmaf chain whatever tile
+// either row falls in (pool_tile.h), the same bits for (n, j) and (j, n); the two norms meet in one float32 addition, which
+// commutes: t(n, j) and t(j, n) are the same bits and the graph is symmetric.
 //
 // Launches, all on the caller's stream, whose order is the ONLY ordering between workgroups (no cooperative launch, no grid
 // barrier, no atomics, nothing read back):
-//   pb_norm_kernel   |x_j|^2 of every row, one wave per row, in the summation order of batch_rows.h (kn_norm_kernel's arithmetic)
-//   pb_tile_kernel   kn_list_kernel's geometry: workgroup = 128 rows (4 waves x 32), the pool in tiles of 128 candidates (4 MFMA
-//                    row blocks of 32 per wave), both operands through LDS in chunks of 32 columns, the pair form taking |l - r|
-//                    while staging, the tile's norms and groups (-1: not eligible) beside them.  Lane (l, h) of a wave holds for
-//                    row l the 16 candidates 8 g + 4 h + i of each block.  pb_block — the ONE place the score is formed and the
-//                    edge decided — gives the lane's 16 decisions as bits at their candidate positions of a 32-bit mask.
+//   pt_norm_kernel   (pool_tile.h) |x_j|^2 of every row, one wave per row, in the summation order of batch_rows.h
+//   pb_tile_kernel   pt_product per tile of 128 candidates, the tile's norms and groups (-1: not eligible) staged beside the
+//                    operands.  Lane (l, h) of a wave holds for row l the 16 candidates 8 g + 4 h + i of each block.  pb_block —
+//                    the ONE place the score is formed and the edge decided — gives the lane's 16 decisions as bits at their
+//                    candidate positions of a 32-bit mask.
 //                    Counting form: popc of the mask, and (with groups) the running minimum over rows of another group; the two
 //                    lanes of a row (lane ^ 32) add their counts and combine their minima on (t, j) at the end.
 //                    Filling form: the two lanes OR their masks, a lane writes its candidate c at offsets[n] + base + popc(mask
@@ -30,45 +29,14 @@
 // Measured: DESIGN.md §9.  Not built: distances stored with the edges, skipping tiles by a spatial bound, an incremental-degree
 // greedy, a cosine metric, balls round a separate set of centres (knn_rect.hip has the rectangular product, for lists of K, not
 // for balls), several ranks' pools in one call.
-#include "batch_rows.h"
+#include "pool_tile.h"
 
 namespace alink {
 namespace {
 
-constexpr int PB_TN = 128;                 // rows of a workgroup: 32 per wave
-constexpr int PB_TK = 128;                 // candidates of a tile: four MFMA row blocks per wave
-constexpr int PB_DC = 32;                  // columns of a chunk in LDS
-constexpr int PB_LD = PB_TN + 4;           // LDS row pitch (floats): column e of the tile at e * PB_LD
 constexpr int MC_ROWS = 64;                // rows of a chunk of the recount: 16 per wave
 
 enum { PB_DEGREE = 0, PB_OTHER = 1, PB_FILL = 2 };
-
-__device__ __forceinline__ float pb_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
-}
-
-// |x_n|^2: the squared distance of row n to the zero row in the order of batch_rows.h.  One wave per row.
-template <bool PAIR, bool VEC>
-__global__ __launch_bounds__(256) void pb_norm_kernel(const RbRows t, long long N, float* __restrict__ xnorm) {
-    const int lane = threadIdx.x & 63;
-    const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= N) return;
-    const RbRow r = rb_row<PAIR>(t, n);
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    float s = 0.f;
-    for (int e0 = 4 * lane; e0 < t.D; e0 += 256) s = rb_acc(s, rb_quad<PAIR, VEC>(r, e0, t.D), zero);
-    s = pb_wave_sum(s);
-    if (lane == 0) xnorm[n] = s;
-}
-
-// columns e0 .. e0 + 3 of a tile row; absent rows and columns are zeros
-template <bool PAIR, bool VEC>
-__device__ __forceinline__ float4 pb_fetch(const RbRows& t, long long n, bool have, int e0) {
-    if (!have || e0 >= t.D) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return rb_quad<PAIR, VEC>(rb_row<PAIR>(t, n), e0, t.D);
-}
 
 // The score and the edge test, the same code in the counting and the filling pass.  One float32 addition (it commutes), one
 // fused rounding: t(n, j) and t(j, n) are the same bits.
@@ -121,15 +89,13 @@ struct PbOut {
 template <int MODE, bool PAIR, bool VEC>
 __global__ __launch_bounds__(256, 2) void pb_tile_kernel(const RbRows t, long long N, const float* __restrict__ xnorm,
                                                           const int32_t* __restrict__ group, const PbOut o) {
-    __shared__ float sX[PB_DC * PB_LD];
-    __shared__ float sC[PB_DC * PB_LD];
-    __shared__ __attribute__((aligned(16))) float sN[PB_TK];
-    __shared__ __attribute__((aligned(16))) int sG[PB_TK];
-    const int D = t.D;
+    __shared__ float sX[PT_DC * PT_LD];
+    __shared__ float sC[PT_DC * PT_LD];
+    __shared__ __attribute__((aligned(16))) float sN[PT_TK];
+    __shared__ __attribute__((aligned(16))) int sG[PT_TK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-    const long long n0 = (long long)blockIdx.x * PB_TN;
-    // staging: thread -> tile row (tid & 127), column quads (tid >> 7) + 2 q, q = 0 .. 3
-    const int srow = tid & 127, sq0 = tid >> 7;
+    const long long n0 = (long long)blockIdx.x * PT_TN;
+    const int srow = tid & 127;            // the tile row this thread stages (pool_tile.h)
     const long long xn = n0 + srow;
     const bool xhave = xn < N;
 
@@ -154,59 +120,19 @@ __global__ __launch_bounds__(256, 2) void pb_tile_kernel(const RbRows t, long lo
         if (n < N) { o0 = o.offsets[n]; o1 = o.offsets[n + 1]; }
     }
 
-    for (long long k0 = 0; k0 < N; k0 += PB_TK) {
+    for (long long k0 = 0; k0 < N; k0 += PT_TK) {
         const long long left = N - k0;
-        const int nblk = left >= PB_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
+        const int nblk = left >= PT_TK ? 4 : (int)((left + 31) >> 5);      // MFMA row blocks of this tile that hold a row (uniform)
         const long long cn_ = k0 + srow;
         const bool chave = cn_ < N;
         f32x16 acc[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[b][i] = 0.f;
-        for (int d0 = 0; d0 < D; d0 += PB_DC) {
-            float4 vx[4], vc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e0 = d0 + 4 * (sq0 + 2 * q);
-                vx[q] = pb_fetch<PAIR, VEC>(t, xn, xhave, e0);
-                vc[q] = pb_fetch<PAIR, VEC>(t, cn_, chave, e0);
-            }
-            __syncthreads();                               // the previous chunk's operands (and the tile's norms, groups) are read
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = 4 * (sq0 + 2 * q);
-                sX[(c + 0) * PB_LD + srow] = vx[q].x; sX[(c + 1) * PB_LD + srow] = vx[q].y;
-                sX[(c + 2) * PB_LD + srow] = vx[q].z; sX[(c + 3) * PB_LD + srow] = vx[q].w;
-                sC[(c + 0) * PB_LD + srow] = vc[q].x; sC[(c + 1) * PB_LD + srow] = vc[q].y;
-                sC[(c + 2) * PB_LD + srow] = vc[q].z; sC[(c + 3) * PB_LD + srow] = vc[q].w;
-            }
-            if (d0 == 0 && tid < PB_TK) {
-                const long long j = k0 + tid;
-                const float nj = j < N ? xnorm[j] : INFINITY;
-                const int gj = j < N ? (group ? group[j] : 0) : -1;
-                sN[tid] = nj;
-                sG[tid] = (gj < 0 || !(nj < INFINITY)) ? -1 : gj;          // -1: not eligible (or past the pool) — in nobody's ball
-            }
-            __syncthreads();
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                float xv[8], cv[4][8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int e = 16 * half + 2 * i + hh;
-                    xv[i] = sX[e * PB_LD + wave * 32 + l31];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) cv[b][i] = sC[e * PB_LD + b * 32 + l31];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (b < nblk) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(cv[b][i], xv[i], acc[b], 0, 0, 0);
-                }
-            }
-        }
+        pt_product<PAIR, VEC, PAIR, VEC>(t, xn, xhave, t, cn_, chave, nblk, sX, sC, acc, [&](int i) {
+            const long long j = k0 + i;
+            const float nj = j < N ? xnorm[j] : INFINITY;
+            const int gj = j < N ? (group ? group[j] : 0) : -1;
+            sN[i] = nj;
+            sG[i] = (gj < 0 || !(nj < INFINITY)) ? -1 : gj;                // -1: not eligible (or past the pool) — in nobody's ball
+        });
         const int jbase = (int)(unsigned)k0 + 4 * hh;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -268,15 +194,15 @@ __global__ __launch_bounds__(256) void pb_flag_sum_kernel(const int32_t* __restr
 
 template <int MODE, bool PAIR, bool VEC>
 void pb_enqueue(const RbRows& t, long long N, const int32_t* group, const PbOut& o, float* xnorm, hipStream_t st) {
-    hipLaunchKernelGGL((pb_norm_kernel<PAIR, VEC>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, t, N, xnorm);
-    hipLaunchKernelGGL((pb_tile_kernel<MODE, PAIR, VEC>), dim3((unsigned)((N + PB_TN - 1) / PB_TN)), dim3(256), 0, st, t, N, xnorm, group, o);
+    hipLaunchKernelGGL((pt_norm_kernel<PAIR, VEC>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, t, N, xnorm);
+    hipLaunchKernelGGL((pb_tile_kernel<MODE, PAIR, VEC>), dim3((unsigned)((N + PT_TN - 1) / PT_TN)), dim3(256), 0, st, t, N, xnorm, group, o);
     if (MODE == PB_FILL) hipLaunchKernelGGL(pb_flag_sum_kernel, dim3(1), dim3(256), 0, st, o.flag, N, (int32_t*)o.deg);
 }
 
 template <int MODE>
 void pb_dispatch(const RbRows& t, long long N, const int32_t* group, const PbOut& o, float* xnorm, hipStream_t st) {
     const bool pair = t.li != nullptr;
-    const bool vec = t.D % 4 == 0 && (((uintptr_t)t.x | (pair ? (uintptr_t)t.r : 0)) & 15) == 0;
+    const bool vec = pt_vec(t);
     if (pair) { if (vec) pb_enqueue<MODE, true, true>(t, N, group, o, xnorm, st); else pb_enqueue<MODE, true, false>(t, N, group, o, xnorm, st); }
     else { if (vec) pb_enqueue<MODE, false, true>(t, N, group, o, xnorm, st); else pb_enqueue<MODE, false, false>(t, N, group, o, xnorm, st); }
 }
@@ -366,7 +292,6 @@ __global__ __launch_bounds__(256) void mc_pick_kernel(const long long* __restric
     }
 }
 
-size_t pb_align(size_t b) { return (b + 255) & ~(size_t)255; }
 long long mc_chunks(long long N) { return (N + MC_ROWS - 1) / MC_ROWS; }
 
 int pb_check_pool(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D, float radius2,
@@ -389,7 +314,7 @@ extern "C" {
 
 size_t alink_ball_scratch_bytes(int64_t N, int D) {
     if (N <= 0 || N >= (1ll << 31) || D <= 0 || D > RB_MAX_D) return 0;
-    return 2 * pb_align((size_t)N * 4);
+    return 2 * pt_align((size_t)N * 4);
 }
 
 int alink_ball_count(const float* dev_x, const float* dev_r, const int32_t* dev_li, const int32_t* dev_ri, int64_t N, int D,
@@ -419,7 +344,7 @@ int alink_ball_fill(const float* dev_x, const float* dev_r, const int32_t* dev_l
     DeviceGuard dg(device_of_pointer(dev_x));
     const RbRows t{dev_x, dev_r, dev_li, dev_ri, D};
     float* xnorm = (float*)dev_scratch;
-    int32_t* flag = (int32_t*)((char*)dev_scratch + pb_align((size_t)N * 4));
+    int32_t* flag = (int32_t*)((char*)dev_scratch + pt_align((size_t)N * 4));
     // (PbOut.deg carries dev_mismatch to the final launch)
     const PbOut o{radius2, dev_mismatch, nullptr, nullptr, (const long long*)dev_offsets, (long long)E, dev_nbr, flag};
     pb_dispatch<PB_FILL>(t, N, dev_group, o, xnorm, (hipStream_t)stream);
@@ -429,7 +354,7 @@ int alink_ball_fill(const float* dev_x, const float* dev_r, const int32_t* dev_l
 
 size_t alink_max_coverage_scratch_bytes(int64_t N, int k) {
     if (N <= 0 || N >= (1ll << 31) || k < 1) return 0;
-    return 2 * pb_align((size_t)mc_chunks(N) * 4);
+    return 2 * pt_align((size_t)mc_chunks(N) * 4);
 }
 
 int alink_max_coverage(const int64_t* dev_offsets, const int32_t* dev_nbr, int64_t N, const int32_t* dev_seed, int64_t S, int k,
@@ -445,7 +370,7 @@ int alink_max_coverage(const int64_t* dev_offsets, const int32_t* dev_nbr, int64
     const long long* off = (const long long*)dev_offsets;
     const long long C = mc_chunks(N);
     int32_t* cdeg = (int32_t*)dev_scratch;
-    int32_t* crow = (int32_t*)((char*)dev_scratch + pb_align((size_t)C * 4));
+    int32_t* crow = (int32_t*)((char*)dev_scratch + pt_align((size_t)C * 4));
     if (S > 0)
         hipLaunchKernelGGL(mc_seed_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, off, dev_nbr, (long long)N, dev_seed, (long long)S,
                            dev_covered);

@@ -98,6 +98,22 @@ def test_a_set_against_itself_gives_alink_knns_lists(gpu, N, D, K):
     assert (ridx == np.arange(N)[:, None]).any(axis=1).mean() > 0.5        # most rows do find themselves
 
 
+@pytest.mark.parametrize("D", [33, 64])
+def test_the_first_neighbour_is_the_k_means_assignment(gpu, D):
+    """real-valued rows: alink_kmeans with no update step assigns every row to argmin_j fma(-2, x . c_j, |c_j|^2), ties to the
+    lower index, and so does the first column of alink_knn_rect at K = 1 against the centres as a row table — one fmaf chain
+    behind both (pool_tile.h), so the two agree index for index, not within a band.  300 rows against 130 centres: two candidate
+    tiles, the second with one partial MFMA block; D = 33 takes scalar loads and a partial chunk, D = 64 the 16-byte loads."""
+    from a_link_amd import cluster
+    rng = np.random.RandomState(1300 + D)
+    X, Cm = rng.randn(300, D).astype(np.float32), rng.randn(130, D).astype(np.float32)
+    X, Cm = X[np.isfinite(X).all(axis=1)], Cm[np.isfinite(Cm).all(axis=1)]
+    assign = cluster.kmeans_device(_dev(X), len(Cm), iters=0, centres=_dev(Cm))["assign"].cpu().numpy()
+    idx, _, found = _run(X, Cm, 1)
+    assert (found == 1).all() and np.array_equal(assign, idx[:, 0])
+    assert len(np.unique(assign)) > 32                                     # the assignment is spread over both tiles' blocks
+
+
 @pytest.mark.parametrize("D", [512, 40, 7])
 def test_pair_form_equals_row_form(gpu, D):
     rng = np.random.RandomState(D)

@@ -48,7 +48,7 @@ def _unit(t):
 
 
 def _slices(N, K):
-    """the slices the update's scan cuts the rows into (kmeans.hip: km_slices)"""
+    """the slices the update's scan cuts the rows into (pool_tile.h: pt_slices)"""
     S = 1 if K >= 2048 else min(64, -(-4096 // K))
     L = -(-(-(-N // S)) // 256) * 256
     return -(-N // L)

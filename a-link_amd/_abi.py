@@ -123,6 +123,7 @@ PROTOTYPES = {
     "alink_head_grads_dev": (_vp, [_vp]),
     "alink_head_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "alink_head_egl": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
+    "alink_head_feature_mix": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "alink_committee_forward": (_i, [C.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "alink_committee_forward_multi": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i64, _vp, _vp]),
     "alink_pair_scores_matrix": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -227,6 +227,34 @@ class Bagging:
         return _cal.cal_device((emb_left, emb_right, li, ri), references, probs, probs.index_select(0, take), n_instances, k_nn=k_nn,
                                exclude=lab)
 
+    def alfamix_indexed(self, emb_left, emb_right, li, ri, labelled, y_labelled, n_instances, eps=0.2, iters=10, seed=None):
+        """Extension: ALFA-Mix queries (alfamix.py; Parvaneh et al. 2022) among the pairs (li[p], ri[p]) gathered from ONE left
+        and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs (indices into
+        li / ri, at least one) that are labelled already and `y_labelled` their classes: the anchors are alfamix.class_anchors
+        of those rows (the labelled rows are copied to the host for it).  A candidate is a pair whose decision ANY member flips
+        under some anchor — the members' flip masks OR-ed; the fill uses the committee's mean probabilities (predict_indexed);
+        labelled pairs are never picked.  -> (picks int32 (n,) on the device, info): alfamix.select_device's picks; info holds
+        "flip", "probs" (device) and "anchors" (float32 array)."""
+        from . import alfamix as _alfamix
+        from .typiclust import _labelled_indices
+        self._one_feature_space(emb_left, emb_right)
+        hs = self._device_heads()
+        if hs is None:
+            raise TypeError("alfamix_indexed needs DenseHead members")
+        lab = _labelled_indices(labelled, int(li.numel()))
+        if len(lab) == 0:
+            raise ValueError("alfamix_indexed needs at least one labelled pair: the anchors are the labelled classes' mean rows")
+        take = hs[0].torch.from_numpy(lab).to(li.device)
+        rows = (emb_left.index_select(0, li.index_select(0, take).long()) - emb_right.index_select(0, ri.index_select(0, take).long())).abs()
+        anchors = _alfamix.class_anchors(rows.cpu().numpy(), y_labelled)
+        flip = None
+        for h in hs:
+            f = _alfamix.feature_mix_device(h, emb_left, emb_right, anchors, li, ri, eps=eps, want=("flip",))["flip"]
+            flip = f if flip is None else flip | f
+        probs = self.predict_indexed(emb_left, emb_right, li, ri)
+        picks = _alfamix.select_device((emb_left, emb_right, li, ri), flip, probs, n_instances, iters=iters, seed=seed, exclude=lab)
+        return picks, {"flip": flip, "probs": probs, "anchors": anchors}
+
     def resize(self, images, new_size):
         """cv2.resize(image, new_size) per image (code/committee.py:22-26); new_size = (width, height)."""
         from . import noise as _noise

@@ -37,27 +37,6 @@ struct HeadEgl {
     float final_div;              // > 0: divide by it after adding (last committee member)
 };
 
-// Sum of squares of every row of a tile image in the packed A-operand layout (element (row, k) at
-// (k >> 3) * ROWP + row * 8 + (k & 1) * 4 + ((k & 7) >> 1)), nk8 blocks of 8 deep.  Thread t works for row t >> 3: it adds the
-// blocks (t & 7), (t & 7) + 8, ... in ascending order, a block in ascending k, and the eight shares meet in an xor butterfly
-// (1, 2, 4), which leaves the same bits on all eight lanes.  The order depends on nk8 alone, not on the row.
-__device__ __forceinline__ float tile_row_sumsq(const float* buf, int nk8) {
-    const int row = threadIdx.x >> 3, part = threadIdx.x & 7;
-    float s = 0.f;
-    for (int k8 = part; k8 < nk8; k8 += 8) {
-        const f32x4 e = *(const f32x4*)(buf + k8 * ROWP + row * 8), o = *(const f32x4*)(buf + k8 * ROWP + row * 8 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            s = fmaf(e[j], e[j], s);
-            s = fmaf(o[j], o[j], s);
-        }
-    }
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    return s;
-}
-
 template <int CT>
 __global__ __launch_bounds__(256, 2) void head_egl_kernel(const HeadEgl p) {
     extern __shared__ __attribute__((aligned(16))) float buf[];

@@ -808,6 +808,8 @@ int ensure_packed(alink_head* h, hipStream_t st) {
                        h->d_w2p, h->h1, h->h2);
     if (h->d_w2tp)
         hipLaunchKernelGGL(pack_transposed_kernel, g1((long long)h->h1 * h->h2), dim3(256), 0, st, src + h->oW2, h->d_w2tp, h->h2, h->h1);
+    if (h->d_w1tp)
+        hipLaunchKernelGGL(pack_transposed_kernel, g1((long long)h->D * h->h1), dim3(256), 0, st, src + h->oW1, h->d_w1tp, h->h1, h->D);
     if (h->qmode && h->d_wt) {      // W1^T, W2^T in bf16 for head_fwd_bf16_kernel
         hipLaunchKernelGGL(transpose_bf16_kernel, g1((long long)h->D * h->h1), dim3(256), 0, st, h->d_pq + h->oW1, h->d_wt,
                            h->D, h->h1);

@@ -1,5 +1,6 @@
 // head_handle.h — the pair head's handle and the constants of its MFMA forward (head.hip), shared with the kernels that run on
-// the same handle from other files (egl.hip): the packed weight copies, the LDS image of a 32-pair tile and how large it is.
+// the same handle from other files (egl.hip, alfamix.hip): the packed weight copies, the LDS image of a 32-pair tile, how large it is,
+// and the row norms read off it.
 #pragma once
 #include "alink_common.h"
 #include "net_host.h"
@@ -21,6 +22,8 @@ struct alink_head {
     float* d_w2p = nullptr;      // W2 packed: [h1/8][h2][2][4]
     float* d_w2tp = nullptr;     // W2^T packed: [h2/8][h1][2][4] — the back-projection of egl.hip; allocated by its first call, then
                                  // re-derived with the other packed copies
+    float* d_w1tp = nullptr;     // W1^T packed: [h1/8][D][2][4] — the back-projection to the input of alfamix.hip; allocated by its
+                                 // first call, then re-derived with the other packed copies
     bool packed_dirty = true;
     // bf16 compute mode (alink_head_set_compute_dtype; BASELINE configs[4] "bf16 fine-tune", mixed precision):
     // master parameters, gradients and Adadelta state stay f32; the forward / backward GEMM operands are bf16 —
@@ -70,6 +73,29 @@ inline size_t fwd_lds_bytes(int h1) {
     if (c > m) m = c;
     return m * sizeof(float);
 }
+
+#ifdef __HIPCC__
+// Sum of squares of every row of a tile image in the packed A-operand layout (element (row, k) at
+// (k >> 3) * ROWP + row * 8 + (k & 1) * 4 + ((k & 7) >> 1)), nk8 blocks of 8 deep.  Thread t works for row t >> 3: it adds the
+// blocks (t & 7), (t & 7) + 8, ... in ascending order, a block in ascending k, and the eight shares meet in an xor butterfly
+// (1, 2, 4), which leaves the same bits on all eight lanes.  The order depends on nk8 alone, not on the row.
+__device__ __forceinline__ float tile_row_sumsq(const float* buf, int nk8) {
+    const int row = threadIdx.x >> 3, part = threadIdx.x & 7;
+    float s = 0.f;
+    for (int k8 = part; k8 < nk8; k8 += 8) {
+        const f32x4 e = *(const f32x4*)(buf + k8 * ROWP + row * 8), o = *(const f32x4*)(buf + k8 * ROWP + row * 8 + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s = fmaf(e[j], e[j], s);
+            s = fmaf(o[j], o[j], s);
+        }
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    return s;
+}
+#endif
 
 // brings the packed copies of W1 / W2 (and the derived copies that exist) up to date with the parameters (head.hip)
 int head_ensure_packed(alink_head* h, hipStream_t st);

@@ -330,6 +330,13 @@ class DenseHead(KerasFitMixin, Handle):
         from . import egl as _egl
         return _egl.expected_gradient_length_device(self, L, R, li, ri, want=want)
 
+    def feature_mix_device(self, L, R, anchors, li=None, ri=None, eps=0.2, want=("probs", "flip")):
+        """EXTENSION (alfamix.py): ALFA-Mix's feature mix of the pairs (L[n], R[n]) or (L[li[n]], R[ri[n]])
+        towards the (A, D) anchors on the device: the probabilities, the mask of anchors that flip the decision, and on request
+        the mixed rows and their probabilities -> {name: CUDA tensor}; alfamix.feature_mix_device's."""
+        from . import alfamix as _alfamix
+        return _alfamix.feature_mix_device(self, L, R, anchors, li, ri, eps=eps, want=want)
+
     def badge_device(self, L, R, li=None, ri=None, n_instances=1, uniforms=None, seed=None):
         """EXTENSION (badge.py): a BADGE batch — k-means++ seeding over the gradient embeddings of the pairs
         (L[n], R[n]) or (L[li[n]], R[ri[n]]) on the device -> (idx int32 (k,), potential float64 (k,)); badge.badge_device's."""

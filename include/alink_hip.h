@@ -673,6 +673,44 @@ int alink_head_egl(alink_head_t* h, const float* dev_L, const float* dev_R, cons
                    float* dev_probs,                       /* [P][od]        or NULL */
                    float* dev_emb,                         /* [P][od*h2]     or NULL */
                    void* stream);
+/* ALFA-Mix (Parvaneh et al. 2022, "Active learning by feature mixing") through one head: does the head's decision for a pair
+ * flip when its feature is pulled a short way towards an anchor (the mean labelled row of a class)?  EXTENSION, no reference
+ * driver calls it.  The pairs are alink_head_forward's (dev_li / dev_ri index the two feature tables, NULL = identity; the
+ * indices are NOT range-checked).  For pair p, d = |L[li[p]] - R[ri[p]]| in float32; z1, a1, z2, a2, z3, probs are exactly
+ * alink_head_forward's; yhat is alink_head_egl's: out_dim 2, p1 > p0 ? 1 : 0; out_dim 1, p > 0.5.
+ * Gradient:
+ *   w = W3[:,0] - W3[:,1]  (out_dim 1: W3[:,0]),   u = w . [z2 > 0],   v = (u W2^T) . [z1 > 0]      (alink_head_egl's u and v)
+ *   q = v W1^T  (D values): the input gradient of z3_0 - z3_1 (out_dim 1: of z3)
+ *   g = the direction that lowers the predicted class's margin — the train loss's input gradient for the label yhat up to a
+ *       positive factor; no clip enters, so saturated rows have a direction too:
+ *       out_dim 2: g = q if yhat = 1, else -q;    out_dim 1: g = -q if yhat = 1, else q;    G = |g|_2
+ * Mix, for anchor a of A (1 .. 8; dev_anchors is an (A, D) float32 table):
+ *   z = anchor_a - d,   Z = |z|_2,   s = eps Z / G,   t_e = s g_e
+ *   delta_e = min(max(t_e, min(z_e, 0)), max(z_e, 0)):  a step of length eps |z| along g, kept per element between the row and
+ *       the anchor — the paper's alpha = eps |z| g / |g| (/) z clamped to [0, 1] and applied as d + alpha (.) z, without the
+ *       division;  G == 0, or G or Z not finite: delta = 0
+ *   mixed_a = d + delta
+ * Second forward: the forward's arithmetic on the row mixed_a in place of |l - r| — the same packed weights, k order, layer-2
+ * split, sum order and softmax expression — gives dev_mixed_probs[p][a][:]; bit a of dev_flip[p] is set when the argmax of
+ * dev_mixed_probs[p][a] (the same tie rule) differs from yhat.  dev_probs are alink_head_forward's bits; dev_mixed are the
+ * mixed rows themselves (tests and diagnostics: P x A x D floats).
+ * float32 throughout, one launch, no atomics; every sum runs in an order fixed by (D, h1, h2, A) alone, and a pair's outputs
+ * do not depend on P or on where the pair stands:
+ *   q_e      one matrix-core chain over k = 0 .. h1 - 1 ascending, two k per instruction (the k order of layers 1 and 2)
+ *   G^2, Z^2 over the D elements: share j of 8 adds the 8-element blocks j, j + 8, ... in ascending order, a block in ascending
+ *            e, one fused multiply-add per element; the eight shares meet in an xor butterfly (1, 2, 4).  z_e = fl(anchor_e -
+ *            d_e) is rounded before it is squared and is the z_e of the clamp.
+ *   G = fl(sqrt(G^2)), Z = fl(sqrt(Z^2)), s = fl(fl(eps Z) / G), t_e = fl(s g_e), mixed_e = fl(d_e + delta_e)
+ * P == 0 writes nothing.  ALINK_EINVAL, nothing launched and no output touched: a NULL head, table or anchors, all four
+ * outputs NULL, P < 0 or above 2^29 - 32, A outside 1 .. 8, eps not finite or < 0, D not a multiple of 8 or above 512 (the mix
+ * holds a whole row in LDS), h1 not in {128, 256, 384, 512}, a head in the bf16 compute mode (this is the exact form). */
+int alink_head_feature_mix(alink_head_t* h, const float* dev_L, const float* dev_R, const int32_t* dev_li, const int32_t* dev_ri,
+                           int64_t P, const float* dev_anchors, int A, float eps,
+                           float* dev_probs,        /* [P][od]        or NULL */
+                           uint8_t* dev_flip,       /* [P]            or NULL */
+                           float* dev_mixed_probs,  /* [P][A][od]     or NULL */
+                           float* dev_mixed,        /* [P][A][D]      or NULL: tests and diagnostics */
+                           void* stream);
 /* k-means++ seeding (Arthur & Vassilvitskii 2007) over N pool rows of D floats: the batch rule of BADGE (Ash et al. 2020) when
  * the rows are alink_head_egl's gradient embeddings.  EXTENSION, no reference driver calls it.  The pool has the two row forms of
  * alink_ranked_batch (dev_li == NULL: dev_x is the (N, D) row table; otherwise row n is |dev_x[dev_li[n]] - dev_r[dev_ri[n]]|,

@@ -190,6 +190,10 @@ PROTOTYPES = {
     "alink_information_density": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "alink_kmeanspp_scratch_bytes": (_sz, [_i64, _i]),
     "alink_kmeanspp": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "alink_fisher_factor": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "alink_bait_scores": (_i, [_vp, _i64, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "alink_bait_select_scratch_bytes": (_sz, [_i64, _i, _i, _i]),
+    "alink_bait_select": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "alink_kmeans_scratch_bytes": (_sz, [_i64, _i, _i]),
     "alink_kmeans": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _i] + [_vp] * 7 + [_vp, _vp]),
     "alink_knn_scratch_bytes": (_sz, [_i64, _i, _i]),

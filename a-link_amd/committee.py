@@ -118,6 +118,34 @@ class Bagging:
             embs.append(_egl.expected_gradient_length_device(h, L, R, li, ri, want=("emb",))["emb"])
         return _badge.kmeans_pp_device(torch.cat(embs, dim=1), n_instances, uniforms=uniforms, seed=seed)
 
+    def bait_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, lam=1.0, over=2):
+        """Extension: a BAIT batch (bait.py; Ash et al. 2021) of the pairs (li[p], ri[p]) gathered from embedding matrices on device.
+        Independent members give a block-diagonal Fisher: a pair's row is the members' Fisher factors side by side (blocks =
+        members, at most 512 columns and 8 members) and its score the sum of the members' scores, each against its own A, B.
+        `labelled` names the pairs (indices into li / ri, or None) that are labelled already: they enter M0 and are never picked.
+        emb_left / emb_right may be lists with one matrix per member, as in egl_indexed.
+        -> (idx int32 (k,), score float32 (k,)) on the device, bait.bait_select_device's."""
+        from . import bait as _bait, egl as _egl
+        hs = self._device_heads()
+        if hs is None:
+            raise TypeError("bait_indexed needs DenseHead members")
+        per_member = isinstance(emb_left, (list, tuple))
+        if per_member and (len(emb_left) != len(hs) or not isinstance(emb_right, (list, tuple)) or len(emb_right) != len(hs)):
+            raise ValueError("%d members but %d / %d feature matrices" % (len(hs), len(emb_left), len(emb_right) if isinstance(emb_right, (list, tuple)) else 1))
+        if len(set(h.h2 for h in hs)) != 1:
+            raise ValueError("bait_indexed needs members of one h2: the blocks of a row have one width")
+        if len(hs) * hs[0].h2 > _bait.MAX_WIDTH:
+            raise ValueError("the committee's Fisher factors have %d columns (%d members x %d), beyond the %d a row may have"
+                             % (len(hs) * hs[0].h2, len(hs), hs[0].h2, _bait.MAX_WIDTH))
+        _bait._check_shape(hs[0].h2, len(hs))
+        torch = hs[0].torch
+        fs = []
+        for m, h in enumerate(hs):
+            L, R = (emb_left[m], emb_right[m]) if per_member else (emb_left, emb_right)
+            out = _egl.expected_gradient_length_device(h, L, R, li, ri, want=("probs", "emb"))
+            fs.append(_bait.fisher_factor_device(out["probs"], out["emb"]))
+        return _bait.bait_factors_device(torch.cat(fs, dim=1), labelled, n_instances, lam=lam, over=over, blocks=len(hs))
+
     def ranked_batch_indexed(self, emb_left, emb_right, li, ri, labeled, n_instances, kind="entropy", alpha=None):
         """Extension: a ranked batch (batch.py; modAL.batch) of n_instances among the pairs (li[p], ri[p]) gathered from ONE
         left and ONE right embedding matrix on device — the utility weighed against each pair's distance, as the row

@@ -343,6 +343,13 @@ class DenseHead(KerasFitMixin, Handle):
         from . import badge as _badge
         return _badge.badge_device(self, L, R, li, ri, n_instances=n_instances, uniforms=uniforms, seed=seed)
 
+    def bait_device(self, L, R, li=None, ri=None, labelled=None, n_instances=1, lam=1.0, over=2):
+        """EXTENSION (bait.py): a BAIT batch — Fisher-information greedy selection over the last layer's rank-one
+        Fisher factors of the pairs (L[n], R[n]) or (L[li[n]], R[ri[n]]) on the device -> (idx int32 (k,), score float32 (k,));
+        bait.bait_device's."""
+        from . import bait as _bait
+        return _bait.bait_device(self, L, R, li, ri, labelled=labelled, n_instances=n_instances, lam=lam, over=over)
+
     def predict(self, X, batch_size=1024, verbose=0):
         """Keras Model.predict([L, R]) (reference code/siamese.py:131).  batch_size is accepted for
         API compatibility; the kernel tiles the pairs itself."""

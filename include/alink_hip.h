@@ -749,6 +749,59 @@ int alink_kmeanspp(const float* dev_x, const float* dev_r, const int32_t* dev_li
                    int32_t* dev_idx,                       /* (k) picks in order, -1 = none */
                    double* dev_potential,                  /* (k) T before each pick; [0] = NaN */
                    void* dev_scratch, void* stream);
+/* EXTENSION — BAIT (Ash, Goel, Krishnamurthy & Kakade 2021): a batch chosen by the Fisher information it adds.
+ * Greedy forward selection of over x k rows, each the row that most reduces tr(M^-1 Phi), then a backward prune to k.  No
+ * reference driver calls it.  For the pair head the last layer's per-label gradients are collinear (two outputs: grad l(x, 0) =
+ * p1 s, grad l(x, 1) = -p0 s with s = [-a2 ; a2]), the per-sample Fisher is the rank-one p0 p1 s s^T, and BAIT over the 2 h2
+ * dimensions with the paper's rank-two trace expression equals BAIT over F = h2 dimensions with ONE factor row per sample and
+ * the same ridge (DESIGN.md §9 derives it).  The pinned rule:
+ *   factor   f is (P, F = h2) from alink_head_egl's dev_probs and dev_emb; yhat is alink_head_egl's, c* the other class.
+ *            Two outputs: f_nj = emb[n, c* h2 + j] * (float)sqrt(2 p_yhat / p_c*), the scale in float64 from the float32
+ *            probabilities, rounded once (= sqrt(2 p0 p1) a2).  One output: f_nj = |emb[n, j]| * (float)(sqrt(p (1 - p)) /
+ *            |p - [p > 0.5]|) (= sqrt(p (1 - p)) a2).  A row with an output outside [1e-7, 1 - 1e-7] (float32 comparisons,
+ *            alink_head_egl's; its emb is zero already) has f = 0.  The bias column is not part of the Fisher.
+ *   blocks   a row may carry m factors side by side, a table (N, m F): independent committee members give a block-diagonal
+ *            Fisher, and the score is the sum of the members' scores, each against its own A, B.  m = 1 is plain BAIT.
+ *            Limits: F a multiple of 8, 8 <= F <= 128, 1 <= m <= 8, m F <= 512.
+ *   Gram     Phi_j = (1 / N_all) sum over pool + labelled of f_j f_j^T, M0_j = lambda I + sum over the labelled of f_j f_j^T and
+ *            B0 = M0^-1 are the caller's (float64, host: a-link_amd/bait.py forms them from a read-back of the factor rows).
+ *   score    alink_bait_scores: per block q_A = f^T A f, q_B = f^T B f against float32 images of A = B Phi B and B.  g = f A:
+ *            float32, one fused multiply-add per k from 0, k ascending (an MFMA accumulator); q = sum over columns c of g_c f_c:
+ *            lane (c % 32) adds its columns c, c + 32, ... by fused multiply-add from 0 in ascending order, the 32 lanes meet in
+ *            an xor butterfly (16, 8, 4, 2, 1; F < 32: the missing lanes hold 0).  sign = +1: term = q_A / (1 + q_B); sign = -1:
+ *            term = q_A / (q_B - 1), and a row with any q_B >= 1 is skipped (its score is NaN).  score = the blocks' terms added
+ *            in ascending order, float32, correctly rounded division.  A row's score is a function of (A, B, f_n) alone: not of N,
+ *            its tile, or its place in the tile.  dev_scores (N) or NULL.  dev_partial_best: ceil(N / ALINK_BAIT_TILE) pairs
+ *            (float score, int32 index), per tile of ALINK_BAIT_TILE rows the free row (dev_free[n] != 0) of largest score, ties
+ *            to the lower index, a NaN never wins; (-inf, 2^31 - 1) for a tile without one.  dev_AB: per block the image of A
+ *            then the image of B, element (k, c) of a matrix at ((k / 8) F + c) 8 + (k % 2) 4 + (k % 8) / 2.  One launch.
+ *   forward  alink_bait_select, t = 0 .. k_forward - 1: one score launch (sign +1), then one launch of one workgroup that
+ *            takes the best of the partial maxima (-1 when there is none: nothing changes then), records it, clears its free
+ *            byte and, per block in float64: w = B f (w_i = sum over k ascending of B[k][i] f_k, fused multiply-adds from 0:
+ *            B is symmetric and row k stands for column k), c = 1 + f^T w, B[i][j] -= (w_i w_j) / c; then C = Phi B and
+ *            A = B C, both as Z[i][j] = sum over k ascending of X[k][i] Y[k][j] by fused multiply-add from 0 (A is RECOMPUTED,
+ *            a function of (B, Phi) alone), and the float32 images of A and B.  dev_Phi and dev_B must be symmetric.
+ *   backward while more than k_keep picks are kept: the same two launches with sign -1 over a table of the picked rows: remove
+ *            the kept row of largest score q_A / (q_B - 1) summed over blocks, ties to the earlier pick; B[i][j] -= (w_i w_j)
+ *            / (f^T w - 1)  (= B + w w^T / (1 - f^T w)).  If every kept row is skipped nothing more is removed, and the first
+ *            k_keep kept picks are returned.  Result: the kept picks in the order they were picked with their forward scores
+ *            (-1 / NaN beyond them); dev_free is 0 exactly on the rows returned and the rows it was 0 on before.
+ *   Deliberately not the authors' code: no nLabeled / (nLabeled + K) rescaling of M0; deterministic ties.
+ * alink_bait_select enqueues 1 + 2 k_forward (+ 2 + 2 (k_forward - k_keep) when k_keep < k_forward) launches on `stream` and
+ * returns: no host synchronisation, no data-dependent loop, no atomics, no workgroup waits on another.  With k_keep == k_forward
+ * there is no prune and dev_B comes back: k1 + k2 forward picks equal two chained calls bit for bit.  Results are bit-identical
+ * from run to run.  ALINK_EINVAL, nothing launched: a NULL argument (dev_scores may be NULL), N outside
+ * 1 .. 2^31 - 1, F / m outside the limits, sign not +-1, od not 1 or 2, k_keep < 1 or k_forward < k_keep or k_forward > N, a row
+ * table or dev_AB not 16-byte aligned, dev_scratch not 256-byte aligned.  Not built: the Gram matrices on the device; per-sample rank above one; an incrementally
+ * updated score (q' = q - (f . w)^2 / c ...), which would make a row's float32 score depend on the pick history. */
+#define ALINK_BAIT_TILE 128   /* rows per tile of alink_bait_scores' partial maxima */
+int alink_fisher_factor(const float* dev_probs, const float* dev_emb, int64_t P, int od, int h2, float* dev_f /* (P, h2) */, void* stream);
+int alink_bait_scores(const float* dev_f, int64_t N, int F, int m, const float* dev_AB, const uint8_t* dev_free, int sign,
+                      float* dev_scores, void* dev_partial_best, void* stream);
+size_t alink_bait_select_scratch_bytes(int64_t N, int F, int m, int k_forward);
+int alink_bait_select(const float* dev_f, int64_t N, int F, int m, const double* dev_Phi /* (m, F, F) */,
+                      double* dev_B /* (m, F, F) in / out */, uint8_t* dev_free /* (N) in / out */, int k_forward, int k_keep,
+                      int32_t* dev_idx /* (k_keep) */, float* dev_score /* (k_keep) */, void* dev_scratch, void* stream);
 /* EXTENSION — Lloyd's k-means of a pool on the device: T iterations from given centres, the engine of k-means
  * sampling and of the diverse mini-batch (a-link_amd/cluster.py).  The pool as alink_kmeanspp takes it: an (N, D) row table dev_x
  * (dev_li == NULL), or row n = |dev_x[dev_li[n]] - dev_r[dev_ri[n]]| formed on the fly.  dev_weight: (N) float32 or NULL (every

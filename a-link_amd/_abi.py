@@ -208,6 +208,10 @@ PROTOTYPES = {
     "alink_ball_fill": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i64, _vp, _vp, _vp, _vp]),
     "alink_max_coverage_scratch_bytes": (_sz, [_i64, _i]),
     "alink_max_coverage": (_i, [_vp, _vp, _i64, _vp, _i64, _i] + [_vp] * 3 + [_vp, _vp]),
+    "alink_facility_scratch_bytes": (_sz, [_i64, _i, _i64, _i]),
+    "alink_facility_gains": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "alink_facility_cover": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
+    "alink_facility_select": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -237,6 +237,42 @@ class Bagging:
         return _probcover.probcover_device((emb_left, emb_right, li, ri), labelled, n_instances, delta=delta, groups=groups, alpha=alpha,
                                            fill=fill, random_state=random_state)
 
+    def facility_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, kind=None, beta=10, eps=0.01, cap=None, fill=None,
+                         random_state=None):
+        """Extension: facility-location queries (facility.py; FASS, Wei, Iyer & Bilmes 2015) among the pairs (li[p], ri[p]) gathered
+        from ONE left and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs
+        (indices into li / ri) that are labelled already: they are covered before the first pick, so never picked.  kind=None:
+        facility location over the whole pool, the members not consulted.  `kind` as in ranked_batch_indexed: FASS — only the
+        beta * k unlabelled pairs of largest utility (and the labelled pairs, as labelled) take part.  eps: the stochastic greedy's
+        (None: the plain greedy, every pair a candidate at every step).  -> (picks int64 NumPy array, info),
+        facility.facility_device's; the picks index li / ri."""
+        from . import facility as _facility, uncertainty as _unc
+        from .typiclust import _labelled_indices
+        self._one_feature_space(emb_left, emb_right)
+        pool = (emb_left, emb_right, li, ri)
+        if kind is None:
+            return _facility.facility_device(pool, labelled, n_instances, cap=cap, eps=eps, fill=fill, random_state=random_state)
+        _facility._check_beta(beta)
+        torch = self._device_heads()[0].torch
+        N = int(li.numel())
+        lab = _labelled_indices(labelled, N)
+        k = _facility._cluster._check_instances(n_instances)
+        utility = self._indexed_utility(emb_left, emb_right, li, ri, kind)
+        free = torch.ones(N, dtype=torch.bool, device=li.device)
+        lab_t = torch.from_numpy(lab).to(li.device)
+        free[lab_t] = False
+        unl = torch.nonzero(free).reshape(-1)
+        m = int(unl.numel()) if beta is None else min(int(unl.numel()), int(beta) * k)
+        if m < 1:
+            raise ValueError("facility_indexed: every pair is labelled")
+        top = unl.index_select(0, _unc.topk_device(utility.index_select(0, unl), m)[0].long())
+        keep = torch.cat([top, lab_t])
+        sub = (emb_left, emb_right, li.index_select(0, keep), ri.index_select(0, keep))
+        picks, info = _facility.facility_device(sub, np.arange(m, m + len(lab)), n_instances, cap=cap, eps=eps, fill=fill,
+                                                random_state=random_state)
+        info["kept"] = keep
+        return keep.cpu().numpy()[picks].astype(np.int64), info
+
     def cal_indexed(self, emb_left, emb_right, li, ri, labelled, n_instances, k_nn=10):
         """Extension: Contrastive Active Learning queries (cal.py; Margatina et al. 2021) among the pairs (li[p], ri[p]) gathered
         from ONE left and ONE right embedding matrix on device, each pair as the row |left - right|; `labelled` names the pairs

@@ -10,8 +10,8 @@ from .learners import ActiveLearner
 
 def get_strategy_object(query_strategy):
     """code/existing_al.py:43-49; 'egl_sampling', 'badge_sampling', 'kmeans_sampling', 'diverse_minibatch_sampling',
-    'typiclust_sampling', 'probcover_sampling', 'cal_sampling', 'alfamix_sampling' and 'bait_sampling' are this package's
-    additions"""
+    'typiclust_sampling', 'probcover_sampling', 'cal_sampling', 'alfamix_sampling', 'bait_sampling' and 'facility_sampling' are
+    this package's additions"""
     if query_strategy == 'uncertainty_sampling':
         return uncertainty.uncertainty_sampling
     elif query_strategy == 'margin_sampling':
@@ -45,6 +45,9 @@ def get_strategy_object(query_strategy):
     elif query_strategy == 'bait_sampling':               # EXTENSION (bait.py)
         from . import bait
         return bait.bait_sampling
+    elif query_strategy == 'facility_sampling':           # EXTENSION (facility.py)
+        from . import facility
+        return facility.facility_sampling
 
 
 def run_baseline(model, dataGen, query_strategy='uncertainty_sampling', active_ratio=1.0, out_model=None, verbose=1,
